@@ -6,6 +6,16 @@ ImageNet-shaped data (BASELINE.json metric / configs[1]; configs[2] for --gpus N
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W             # the driver's line: the ranks are already there
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, proves the graph, times the K steps and prints the line: the
+contract keys, `ms_per_step`, `config`, `compute_roofline`.  Everything measured BESIDE the headline -- the same steps launched
+eagerly and with per-kernel events (`eager_launch_*`, `roofline`, `mrla_kernels`), `forward_only`, `eager_rocm`, `cpu_baseline`,
+`other_configs`, `config.drop_path_0`, `detection_backbone` -- takes runs of its own and waits for `--full` (the paragraphs below
+that describe those keys describe a `--full` run; with a process group -- N > 1, `--ddp-probe` -- the eager regions are taken
+regardless, they are what the line falls back to when a capture fails).  `--dump-outputs DIR` writes what a step of the timed
+path computes from the seeded initial state -- loss, gradients, updated weights -- as DIR/<name>.npy (benchkit/outputs.py).
+MIOpen's solver search of the warm-up steps starts from the records committed under benchkit/miopen_db/ (its README.md): the
+same solvers every run, and 8 s instead of 38 s from start to exit on an empty home directory.
+
 A "step" = forward + loss + backward + SGD update on one synthetic batch already resident in HBM.  On a single GPU the
 timed steps replay the whole step from one HIP graph (`config.launch`; `--graph 0` times PyTorch's kernel-by-kernel
 launches instead) -- AFTER the graph has proven itself: `config.replay_matches_eager` / `config.replay_check` = three
@@ -62,7 +72,8 @@ Besides the contract keys it carries
                    (mmdetection/mmdet/models/backbones/resnet_mrlal.py:283-293), with the eager restatement beside it.
 `--autocast none` times resnet/train.py's own fp32 recipe (:397-409), `fp16` deit/engine.py:37's.
 The parts live in benchkit/: common (flags, the step, the contract's timing), core (one rank's measurement), ranks +
-dataparallel (N > 1), baselines (the legs beside the headline; the only importer of oracle/ besides --eager), report (the line).
+dataparallel (N > 1), baselines (the legs beside the headline, --full; the only importer of oracle/ besides --eager), outputs
+(--dump-outputs), report (the line).
 """
 import os
 import sys
@@ -95,6 +106,13 @@ def main():
     # (TORCH_NCCL_RETHROW_CUDA_ERRORS stays at its default: asynchronous errors of the timed run must surface.)
     for k, v in (("TORCH_NCCL_CUDA_EVENT_CACHE", "0"), ("TORCH_FR_BUFFER_SIZE", "0")):
         os.environ.setdefault(k, v)
+    # MIOpen's solver search (torch.backends.cudnn.benchmark, the warm-up steps) also builds and times its reference ("naive")
+    # convolution kernels: compiled from source where the user's kernel cache is empty, then 0.3 - 0.8 s per launch at these
+    # sizes, several launches per problem -- 18 s of a 36 s run with warm caches, more with cold ones, for solvers that are
+    # three orders of magnitude away from ever being picked.  Left out of the search (the environment wins if it says otherwise).
+    for k in ("FWD", "BWD", "WRW"):
+        os.environ.setdefault("MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_" + k, "0")
+    common.use_committed_miopen_tuning()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.ddp_probe:
         sys.exit(launch_ranks(args))              # (nothing before this line has touched the GPU)
 

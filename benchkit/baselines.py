@@ -22,7 +22,7 @@ def cpu_model_name():
     return "unknown"
 
 
-def cpu_baseline(arch, budget_s=90.0):
+def cpu_baseline(arch, budget_s=60.0):
     """Eager CPU restatement, forward only, b=32 fp32.  The host's fair number: the thread count is
     swept ({16, 32, 64, 128} and the 8 of the survey container, capped at the logical CPUs; after a common warm-up every count
     gets one untimed and THREE timed iterations, the median counts), channels_last is tried at the best count the same way, and
@@ -191,9 +191,9 @@ def forward_only(net, x, steps=10, graph=True):
 
 
 def _child(extra, timeout=900):
-    """`python bench.py <extra> --no-baselines` as a fresh process (its own MIOpen state and HIP graph; this process is idle
+    """`python bench.py <extra> --full --no-baselines` as a fresh process (its own MIOpen state and HIP graph; this process is idle
     meanwhile).  Returns (parsed line or None, error text or None, wall seconds)."""
-    cmd = [sys.executable, BENCH] + extra + ["--no-baselines"]
+    cmd = [sys.executable, BENCH] + extra + ["--full", "--no-baselines"]
     t0 = time.perf_counter()
     try:
         p = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)

@@ -33,7 +33,17 @@ def parse():
     ap.add_argument("--autocast", choices=sorted(AUTOCAST), default="bf16",
                     help="bf16 (BASELINE's metric); none: fp32, resnet/train.py's own recipe (:397-409, no AMP); fp16: deit/engine.py:37")
     ap.add_argument("--shape", default="", help="det_* backbones: the image batch as BxCxHxW (default 2x3x800x1344)")
-    ap.add_argument("--no-baselines", action="store_true", help="skip the cpu_baseline / eager_rocm / other_configs legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: the same steps launched eagerly and "
+                         "with per-kernel events (eager_launch_*, roofline, mrla_kernels), the inference pass, the eager and CPU "
+                         "baselines and the other configurations.  Off by default: a plain single-process run sets up, warms up, "
+                         "times the steps and prints the line (N > 1 and --ddp-probe runs measure their eager regions regardless: "
+                         "they are what the line falls back to when a capture fails)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what a step of the timed path computes from the seeded initial state -- its loss "
+                         "and, as fixed seeded samples, the gradients and the updated weights -- to DIR/<name>.npy (float32; "
+                         "benchkit/outputs.py)")
+    ap.add_argument("--no-baselines", action="store_true", help="--full: skip the cpu_baseline / eager_rocm / other_configs legs")
     ap.add_argument("--no-others", action="store_true",
                     help="skip the child-process legs (other_configs = BASELINE configs 4 and 5, drop_path 0, the detection backbone)")
     ap.add_argument("--sgd-fused", type=int, default=1, help="1: torch.optim.SGD(fused=True) (one pass), 0: the foreach implementation")
@@ -94,6 +104,32 @@ def free_port():
     port = s.getsockname()[1]
     s.close()
     return port
+
+
+MIOPEN_DB = os.path.join(ROOT, "benchkit", "miopen_db")
+
+
+def use_committed_miopen_tuning():
+    """Point MIOpen's user databases (MIOPEN_USER_DB_PATH) at a private copy of benchkit/miopen_db/: the records MIOpen's own
+    solver search and kernel tuning wrote for the convolution problems of the headline workload (benchkit/miopen_db/README.md).
+    With them the warm-up steps look their solvers up instead of measuring ~160 problems again -- 6 s instead of 38 s from
+    start to exit on MI355X -- and, more important for anyone comparing two runs, every run gets the SAME solvers: two searches
+    do not always settle on the same one, and two solvers for one bf16 convolution differ by percents in the gradients.
+    Problems that have no record (other architectures, batches, MIOpen versions: the file names carry device and version) are
+    searched and tuned as ever, into the copy, which goes away with the process.  Returns the directory, or None where the
+    environment already names one or an outside launcher started the ranks (they share the user's own databases)."""
+    if "MIOPEN_USER_DB_PATH" in os.environ or "WORLD_SIZE" in os.environ:
+        return None
+    import atexit
+    import glob
+    import shutil
+    import tempfile
+    d = tempfile.mkdtemp(prefix="mrla_bench_miopen_")
+    for f in glob.glob(os.path.join(MIOPEN_DB, "*.txt")):
+        shutil.copy(f, d)
+    os.environ["MIOPEN_USER_DB_PATH"] = d           # (child processes and self-launched ranks inherit it)
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    return d
 
 
 # ------------------------------------------------------------------------------------------------------------------

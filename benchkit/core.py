@@ -83,12 +83,18 @@ class Run:
         # (a gloo exchange stages through the host: not capturable)
         self.use_graph = args.graph == 1 or (args.graph < 0 and self.dp != "ddp" and (not dist_on or args.backend == "nccl"))
         self.launch_note, self.split_why = "", None
+        # a plain single-process run times its steps and nothing else; the legs beside the headline wait for --full (with a
+        # process group the eager regions are taken regardless: they are what the line falls back to when a capture fails)
+        self.full = bool(args.full) or dist_on
         self._preflight()
         self.x, self.y = synthetic_batch(args)
         self.R = dict(args=args, rank=rank, world=world, seen=seen, dist_on=dist_on, dp=self.dp, layout=self.layout, x=self.x,
                       net=None, exchange=None, schedule=None, ab_ms=None, legs=True, replay=None, rank_ms=None, what=what,
-                      ddp_first=None)
+                      ddp_first=None, full=self.full)
         self.opt = self.step = self.eager_step = self.graph = self.split_graphs = None
+        self.static_loss = None    # the captured step's loss tensor (every replay overwrites it)
+        self.static_grads = None   # --dump-outputs: ... and its gradient tensors, one entry per parameter
+        self.entry = None          # --dump-outputs: the seeded state before the first step (graphs.TrainingState)
         self.eager_record = None   # a finished eager region with the per-kernel events (N > 1 flat: taken before the captures)
         self.launch = "kernel by kernel (PyTorch eager launches)" + self.launch_note
         self.graph_launch = ("one HIP graph per step (captured fwd+loss+bwd" + ("+gradient all-reduce" if dist_on else "")
@@ -256,11 +262,15 @@ class Run:
             self.net = D.wrap_data_parallel(self.net, device_ids=[self.local], force=args.ddp_probe)
         self.opt = sgd((p for p in self.net.parameters() if p.requires_grad), lr=common.DET_LR if self.y is None else 0.1)
         self.eager_step = self.step = self.new_step(self.net, self.opt)
+        if args.dump_outputs and not self.dist_on:           # (extra steps on one rank alone would hang a process group)
+            from mrla_amd import graphs
+            self.entry = graphs.TrainingState(self.net, self.opt)
         self.warm_up(self.step, args.warmup)                      # warm-up without the timer
         if self.use_graph and self.dist_on:
             fb = self.measured_eagerly_first(self.eager_step)
             try:
                 self.graph = self.capture_voted(self.eager_step, "ddp", 11)
+                self.static_loss = self.eager_step.loss
             except CaptureBroken as e:
                 print(f"warning: HIP graph capture of the data-parallel step failed ({e}); reporting the eager steps measured "
                       "before it", file=sys.stderr, flush=True)
@@ -269,7 +279,7 @@ class Run:
                                            launch="kernel by kernel (PyTorch eager launches; the HIP graph capture of the step "
                                                   f"failed -- {str(e)[:200]} -- so this is the eager region timed before the "
                                                   "capture; the communicator was not used again)"))
-            self.R["replay"], ok = self.check(self.eager_step, self.graph.replay, self.eager_step.loss, self.net, "ddp")
+            self.R["replay"], ok = self.check(self.eager_step, self.graph.replay, self.static_loss, self.net, "ddp")
             if ok:
                 self.step, self.launch = self.graph.replay, self.graph_launch
             else:
@@ -281,7 +291,10 @@ class Run:
             try:
                 for attempt in (0, 1):
                     self.graph = capture(self.eager_step, self.dist_on, 2)
-                    self.R["replay"], ok = self.check(self.eager_step, self.graph.replay, self.eager_step.loss, self.net,
+                    self.static_loss = self.eager_step.loss
+                    # (the gradients the replays write: the eager steps of the check below put their own into .grad)
+                    self.static_grads = [p.grad for p in self.net.parameters()] if args.dump_outputs else None
+                    self.R["replay"], ok = self.check(self.eager_step, self.graph.replay, self.static_loss, self.net,
                                                       f"n1/{attempt}")
                     if ok:
                         self.step, self.launch = self.graph.replay, self.graph_launch
@@ -309,8 +322,20 @@ class Run:
         else:
             dt = timed(self.step, args.steps, 0)             # eager launches as a training loop issues them (no events)
             R["rank_ms"] = dict(common.RANK_MS) if self.dist_on else None
+        dumped = None
+        if args.dump_outputs and self.rank == 0:             # what a step of the timed path computes, before anything else runs
+            from . import outputs
+            graph_timed = self.step is not self.eager_step
+            if self.entry is not None:                       # (see benchkit/outputs.py: why not the free-running state)
+                torch.cuda.synchronize()
+                self.entry.restore(zero_new_state=True)
+                self.warm_up(self.step, outputs.STEPS_FROM_SEEDED_STATE)
+            dumped = outputs.snapshot(self.net, self.static_loss if graph_timed else self.eager_step.loss,
+                                      self.static_grads if graph_timed and self.graph is not None else None)
         if self.eager_record is not None:                    # the eager regions were taken before the captures
             timer, dt_eager, dt_events = self.eager_record["timer"], self.eager_record["dt"], self.eager_record["dt_events"]
+        elif not self.full:
+            dt_eager = dt_events = None                      # (--full: the eager regions beside the headline)
         else:
             # the same `steps` steps launched kernel by kernel: what resnet/train.py's loop gets unchanged ...
             dt_eager = timed(self.eager_step, args.steps, 0) if use_graph else dt
@@ -321,6 +346,8 @@ class Run:
             Fm.TIMER = None
         R["dt_events"] = dt_events
         in_sync, finite = self.states_after()
+        if dumped is not None:
+            outputs.write(args.dump_outputs, dumped)
         if prefer_ddp_line(self, dt, ddp, self.launch):
             pass                                             # (never worse than resnet/train.py:174 unchanged: tier 0's line stands)
         elif self.rank == 0:

@@ -2,6 +2,8 @@
 is loaded, and the contract keys."""
 import json
 import os
+import sys
+import time
 
 import torch
 
@@ -84,6 +86,14 @@ def is_path_kernel(name):
     return name.startswith(("mrla_light_", "mrla_base_", "mrla_token_", "mrla_reduce_rows2"))
 
 
+def _leg(name, fn, *a, **kw):
+    """One leg beside the headline (--full), with its wall time on stderr: the whole run has a budget."""
+    t0 = time.perf_counter()
+    res = fn(*a, **kw)
+    print(f"note: --full: {name} took {time.perf_counter() - t0:.0f} s", file=sys.stderr, flush=True)
+    return res
+
+
 def report(R, emit=True):
     """Rank 0: build the ONE JSON line from a finished measurement R (see main()), print it (emit) and return it."""
     from . import baselines
@@ -91,6 +101,7 @@ def report(R, emit=True):
     dt, dt_eager, timer, launch, use_graph = R["dt"], R["dt_eager"], R["timer"], R["launch"], R["use_graph"]
     exchange, schedule, ab_ms, layout, net, x = R["exchange"], R["schedule"], R["ab_ms"], R["layout"], R["net"], R["x"]
     ips = world * args.batch * args.steps / dt
+    full = R.get("full", True)      # False: a plain run -- the timed steps alone, nothing measured beside them (--full)
     ks = timer.summary()
     path_k = {k: v for k, v in ks.items() if is_path_kernel(k)}
     big = {k: v for k, v in path_k.items() if v["bytes"] > 0}
@@ -152,16 +163,17 @@ def report(R, emit=True):
                       "path": "eager restatement" if args.eager else
                               f"mrla_amd (HIP MRLA tails incl. shortcut add+ReLU, HIP BatchNorm+ReLU(+stem max-pool), HIP MFMA GEMMs for the "
                               f"1x1 convolutions fwd / dgrad / wgrad where eligible, stock 3x3 / 7x7 / strided convolutions; {layout})"},
-           "eager_launch_ms_per_step": round(1e3 * dt_eager / args.steps, 3),
+           **({"eager_launch_ms_per_step": round(1e3 * dt_eager / args.steps, 3)} if dt_eager is not None else {}),
            **({"eager_launch_with_kernel_events_ms_per_step": round(1e3 * R["dt_events"] / args.steps, 3)}
               if R.get("dt_events") is not None else {}),
            # what resnet/train.py gets UNCHANGED (its loop launches the step eagerly, :387-409); `value` is the same step
            # replayed from one HIP graph -- mrla_amd.graphed_step(model, optimizer, criterion, (images, target)), INTEGRATION.md
-           "eager_launch_images_per_sec": round(world * args.batch * args.steps / dt_eager, 1),
-           "roofline": roofline,
-           "mrla_kernels": {k: {"launches": v["launches"], "ms_per_step": round(v["ms"] / args.steps, 3),
-                                **({"GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} if v["bytes"] else {})}
-                            for k, v in ks.items()}}
+           **({"eager_launch_images_per_sec": round(world * args.batch * args.steps / dt_eager, 1)} if dt_eager is not None else {}),
+           # (both from the region with the per-kernel events: --full)
+           **({"roofline": roofline,
+               "mrla_kernels": {k: {"launches": v["launches"], "ms_per_step": round(v["ms"] / args.steps, 3),
+                                    **({"GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)} if v["bytes"] else {})}
+                                for k, v in ks.items()}} if full else {})}
     if args.arch in MODEL_GFLOP_PER_IMAGE:
         tf = ips * MODEL_GFLOP_PER_IMAGE[args.arch] / 1e3
         out["compute_roofline"] = {"model_tflops": round(tf, 1), "peak_bf16_mfma_tflops": MFMA_BF16_PEAK_TFLOPS * world,
@@ -170,12 +182,13 @@ def report(R, emit=True):
                                    "note": "whole-model flops (MIOpen convolutions); the MRLA kernels are HBM/VALU work"}
     if R.get("ddp_first") is not None:
         out["config"]["ddp_eager_first"] = R["ddp_first"]
-    if world == 1 and R["legs"] and not args.no_forward_only and not args.arch.startswith("det_"):
-        out["forward_only"] = baselines.forward_only(net, x, graph=use_graph)
-    if world == 1 and R["legs"] and not dist_on and args.arch.startswith("det_"):
-        out["eager_rocm"] = baselines.eager_rocm_detection(x)
-    elif world == 1 and R["legs"] and not dist_on and not args.no_baselines:
-        out["eager_rocm"] = baselines.eager_rocm(args.arch, args.batch, args.drop_path)
+    legs = R["legs"] and full
+    if world == 1 and legs and not args.no_forward_only and not args.arch.startswith("det_"):
+        out["forward_only"] = _leg("forward_only", baselines.forward_only, net, x, graph=use_graph)
+    if world == 1 and legs and not dist_on and args.arch.startswith("det_"):
+        out["eager_rocm"] = _leg("eager_rocm", baselines.eager_rocm_detection, x)
+    elif world == 1 and legs and not dist_on and not args.no_baselines:
+        out["eager_rocm"] = _leg("eager_rocm", baselines.eager_rocm, args.arch, args.batch, args.drop_path)
         # like for like: both sides launched kernel by kernel by PyTorch (the eager restatement is never graph-replayed);
         # the graph-replayed product forward against the same denominator is reported beside it, labelled
         fo, den = out.get("forward_only"), out["eager_rocm"]["fwd_images_per_sec"]
@@ -183,16 +196,16 @@ def report(R, emit=True):
             fo["vs_eager_rocm"] = round(fo.get("eager_launch_fwd_images_per_sec", fo["fwd_images_per_sec"]) / den, 2)
             if "graph_fwd_images_per_sec" in fo:
                 fo["graph_replay_vs_eager_rocm"] = round(fo["graph_fwd_images_per_sec"] / den, 2)
-        out["cpu_baseline"] = baselines.cpu_baseline(args.arch)
+        out["cpu_baseline"] = _leg("cpu_baseline", baselines.cpu_baseline, args.arch)
         if not args.no_others and (args.arch, args.batch, args.autocast) == ("resnet50_mrlal", 256, "bf16"):
             # this process goes idle: give its graph pool and cached blocks back first
             R["net"] = net = None
             import gc
             gc.collect()
             torch.cuda.empty_cache()
-            out["config"]["drop_path_0"] = baselines.run_drop_path_0(args.arch, args.batch)
-            out["other_configs"] = baselines.run_other_configs()
-            out["detection_backbone"] = baselines.run_detection_backbone()
+            out["config"]["drop_path_0"] = _leg("drop_path_0", baselines.run_drop_path_0, args.arch, args.batch)
+            out["other_configs"] = _leg("other_configs", baselines.run_other_configs)
+            out["detection_backbone"] = _leg("detection_backbone", baselines.run_detection_backbone)
     line = json.dumps(out)
     if emit:
         print(line, flush=True)

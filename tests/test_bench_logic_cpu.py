@@ -121,3 +121,97 @@ def test_counter_passes_are_tied_to_the_library(tmp_path, monkeypatch):
     assert bench.pmc_traffic(A, "mrla_light_apply_bwd")[2] == "stale"
     path.unlink()
     assert bench.pmc_traffic(A, "mrla_light_apply_bwd") == (None, None, None)
+
+
+def _record(monkeypatch, argv, **more):
+    """What core.Run hands report() for a single-process run whose 4 timed steps of 256 images took 0.2 s (no GPU needed)."""
+    import torch
+    from benchkit import common
+    from mrla_amd import functional as Fm
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    args = common.parse()
+    R = dict(args=args, rank=0, world=1, seen=1, dist_on=False, dp="none", layout="channels_last", x=torch.zeros(1, 3, 224, 224),
+             net=None, exchange=None, schedule=None, ab_ms=None, legs=True, replay=None, rank_ms=None, what="fwd+bwd+SGD",
+             ddp_first=None, full=bool(args.full), dt=0.2, dt_eager=None, dt_events=None, timer=Fm.KernelTimer(), use_graph=True,
+             launch="one HIP graph per step", in_sync=None, finite=True)
+    R.update(more)
+    return R
+
+
+def test_a_plain_run_prints_the_headline_and_measures_nothing_beside_it(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is run several times per change: its line carries the contract keys and
+    `ms_per_step`, and none of the legs that take runs of their own -- those wait for --full (report() would have to touch a
+    GPU, the host cores or a child process to produce them: none is there for it here)."""
+    from benchkit import baselines
+    for leg in ("forward_only", "eager_rocm", "eager_rocm_detection", "cpu_baseline", "run_drop_path_0", "run_other_configs",
+                "run_detection_backbone"):
+        monkeypatch.setattr(baselines, leg, lambda *a, **k: pytest.fail("a leg beside the headline ran in a plain run"))
+    rec = json.loads(bench_report.report(_record(monkeypatch, ["--gpus", "1", "--steps", "4", "--warmup", "1"]), emit=False))
+    assert rec["metric"] == "images/sec fwd+bwd resnet50_mrlal b=256" and rec["unit"] == "images/sec"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["steps"] == 4 and rec["warmup"] == 1
+    assert rec["ms_per_step"] == 50.0 and rec["value"] == 256 * 4 / 0.2
+    for key in ("roofline", "mrla_kernels", "eager_launch_ms_per_step", "eager_launch_images_per_sec", "forward_only", "eager_rocm",
+                "cpu_baseline", "other_configs", "detection_backbone"):
+        assert key not in rec, key
+    assert "drop_path_0" not in rec["config"]
+
+
+def test_full_moves_nothing_out_of_the_line(monkeypatch):
+    """--full: every leg beside the headline is asked for, in the line under the key it always had."""
+    from benchkit import baselines
+    for leg in ("forward_only", "eager_rocm", "cpu_baseline", "run_drop_path_0", "run_other_configs", "run_detection_backbone"):
+        monkeypatch.setattr(baselines, leg, lambda *a, _leg=leg, **k: {"leg": _leg, "fwd_images_per_sec": 1.0})
+    monkeypatch.setattr("torch.cuda.empty_cache", lambda: None)
+    rec = json.loads(bench_report.report(_record(monkeypatch, ["--steps", "4", "--full"], dt_eager=0.25, dt_events=0.3), emit=False))
+    assert rec["ms_per_step"] == 50.0 and rec["eager_launch_ms_per_step"] == 62.5 and "roofline" in rec and "mrla_kernels" in rec
+    assert rec["forward_only"]["leg"] == "forward_only" and rec["eager_rocm"]["leg"] == "eager_rocm"
+    assert rec["cpu_baseline"]["leg"] == "cpu_baseline" and rec["config"]["drop_path_0"]["leg"] == "run_drop_path_0"
+    assert rec["other_configs"]["leg"] == "run_other_configs" and rec["detection_backbone"]["leg"] == "run_detection_backbone"
+    # ... and the child processes of those legs are --full runs themselves (they report roofline / eager_rocm to their parent)
+    seen = {}
+
+    def no_child(cmd, **k):
+        seen["cmd"] = cmd
+        raise baselines.subprocess.TimeoutExpired(cmd, 0)
+    monkeypatch.setattr(baselines.subprocess, "run", no_child)
+    assert baselines._child(["--arch", "resnet101_mrlab"])[0] is None
+    assert "--full" in seen["cmd"] and "--no-baselines" in seen["cmd"]
+
+
+def test_dumped_outputs_are_the_same_positions_every_time(tmp_path):
+    """--dump-outputs: vectors above SAMPLE elements are written as one fixed, seeded, sorted sample; small ones whole; float32."""
+    import numpy as np
+    import torch
+    from benchkit import outputs
+    big = [torch.arange(outputs.SAMPLE, dtype=torch.float32), torch.arange(outputs.SAMPLE, 3 * outputs.SAMPLE, dtype=torch.float32)]
+    a, b = outputs._flat_sample(big), outputs._flat_sample([t.clone() for t in big])
+    assert a.dtype == np.float32 and a.shape == (outputs.SAMPLE,) and np.array_equal(a, b) and np.all(np.diff(a) >= 0)
+    assert a.max() > 2 * outputs.SAMPLE                              # (drawn from the whole vector, not from its head)
+    small = outputs._flat_sample([torch.ones(3, 2), torch.zeros(4)])
+    assert small.tolist() == [1.0] * 6 + [0.0] * 4
+    outputs.write(str(tmp_path / "d"), {"loss": np.float32([1.5]), "weights": small})
+    assert np.load(tmp_path / "d" / "loss.npy").tolist() == [1.5] and np.load(tmp_path / "d" / "weights.npy").dtype == np.float32
+    assert 3 * 4 * outputs.SAMPLE <= 64 << 20
+
+
+def test_committed_miopen_records_go_into_a_private_directory(monkeypatch):
+    """bench.py hands MIOpen a COPY of benchkit/miopen_db/ (it writes into its user databases), never the committed files; an
+    environment that names its own directory, or an outside launcher's ranks, keep what they have."""
+    from benchkit import common
+    committed = sorted(f for f in os.listdir(common.MIOPEN_DB) if f.endswith(".txt"))
+    assert len(committed) == 2 and all(f.startswith("gfx950") for f in committed)
+    monkeypatch.delenv("MIOPEN_USER_DB_PATH", raising=False)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    d = common.use_committed_miopen_tuning()
+    try:
+        assert os.environ["MIOPEN_USER_DB_PATH"] == d and os.path.realpath(d) != os.path.realpath(common.MIOPEN_DB)
+        assert sorted(os.listdir(d)) == committed
+        for f in committed:
+            assert open(os.path.join(d, f), "rb").read() == open(os.path.join(common.MIOPEN_DB, f), "rb").read()
+        assert common.use_committed_miopen_tuning() is None and os.environ["MIOPEN_USER_DB_PATH"] == d
+    finally:
+        import shutil
+        shutil.rmtree(d, ignore_errors=True)
+        monkeypatch.delenv("MIOPEN_USER_DB_PATH", raising=False)
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    assert common.use_committed_miopen_tuning() is None and "MIOPEN_USER_DB_PATH" not in os.environ
