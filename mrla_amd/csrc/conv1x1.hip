@@ -17,8 +17,11 @@
 //     v_permlane32_swap between the two half-waves leaves every lane with 16-byte pieces of its pixel's output row;
 //     a wave-private LDS tile [32 pixels][64 channels] then turns them into stores of whole 128-byte lines (8 lanes
 //     per pixel) -- 32-byte fragments per pixel straight from the lanes cost the L2 four requests per line;
-//   * the BatchNorm moments are per-lane running sums over the wave's pixels (register = channel), reduced across
-//     lanes and pixel-waves once at the end of the kernel and written as one partial row per workgroup.
+//   * the BatchNorm moments are per-lane running sums taken where the lines are stored: a store lane reads the same 8
+//     channels of 4 pixel rows of every block back from the tile, so 8 (sum, sum of squares, pivot) triples per lane
+//     cover the wave's 64 channels (in the accumulator layout, one triple per accumulator register = 96 registers, the
+//     K = 256 instance spilled); they are reduced across lanes and pixel-waves once at the end of the kernel and written
+//     as one partial row per workgroup.
 #include <algorithm>
 
 #include "mrla_device.h"
@@ -62,12 +65,11 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
   }
   __syncthreads();
 
-  // moments about a pivot (this wave's first output of the channel), see conv1x1_wide.hip
-  float s1[2][16], s2[2][16], pv[2][16];
+  // moments about a pivot (this wave's first output of the channel), see conv1x1_wide.hip; taken on the store lanes:
+  // a lane keeps the 8 channels of ITS 16-byte piece of the output lines, the same piece for every block of the wave
+  float s1[8], s2[8], pv[8];
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { s1[t][i] = 0.f; s2[t][i] = 0.f; pv[t][i] = 0.f; }
+  for (int i = 0; i < 8; ++i) { s1[i] = 0.f; s2[i] = 0.f; pv[i] = 0.f; }
   bool have_pivot = false;
   int npix = 0;                                     // pixels this wave accumulated (wave-uniform)
 
@@ -87,7 +89,6 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
     if constexpr (DB) {
       if (blk + stride < nblk) load_x(reinterpret_cast<u32x4(&)[KC]>(xn), blk + stride, 0);
     }
-    const bool live = blk * 32 + r < M;                      // this lane's pixel exists (ragged last block)
     npix += min(32, M - blk * 32);
     f32x16 acc[2];
 #pragma unroll
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      // round to bf16 (pairs of neighbouring channels), statistics of the rounded values
+      // round to bf16 (pairs of neighbouring channels)
       unsigned p[8];
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -119,19 +120,6 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
         pr[0] = from_f<bf16_t>(acc[t][2 * i]);
         pr[1] = from_f<bf16_t>(acc[t][2 * i + 1]);
         p[i] = __builtin_bit_cast(unsigned, pr);
-      }
-      if (MOM) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float lo = __uint_as_float(p[i] << 16), hi = __uint_as_float(p[i] & 0xffff0000u);
-          if (!have_pivot) {       // (wave-uniform) first block of this wave: pixel 0 of the half-wave always exists
-            pv[t][2 * i] = __shfl(lo, h * 32, kWave);
-            pv[t][2 * i + 1] = __shfl(hi, h * 32, kWave);
-          }
-          const float dl = live ? lo - pv[t][2 * i] : 0.f, dh = live ? hi - pv[t][2 * i + 1] : 0.f;
-          s1[t][2 * i] += dl;     s2[t][2 * i] = fmaf(dl, dl, s2[t][2 * i]);
-          s1[t][2 * i + 1] += dh; s2[t][2 * i + 1] = fmaf(dh, dh, s2[t][2 * i + 1]);
-        }
       }
       // lane half 0 holds channels {0-3, 8-11, 16-19, 24-27} of its pixel, half 1 the other four groups; after the
       // swaps half 0 holds {0-7, 16-23} and half 1 {8-15, 24-31}: two 16-byte pieces per lane
@@ -151,18 +139,35 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
       *reinterpret_cast<u32x4*>(orow) = (u32x4){p[0], p[1], p[2], p[3]};
       *reinterpret_cast<u32x4*>(orow + 32) = (u32x4){p[4], p[5], p[6], p[7]};
     }
-    have_pivot = true;
-    // whole lines out: 8 lanes per pixel (64 channels = 128 bytes), 8 pixels per store instruction
+    // whole lines out: 8 lanes per pixel (64 channels = 128 bytes), 8 pixels per store instruction; the statistics are
+    // those of the rounded values the lane stores (4 pixel rows of its 8 channels per block; rows past M: neither)
     {
       const int px = lane >> 3, piece = lane & 7;
       bf16_t* ybase = Y + (size_t)blk * 32 * N + n_slice0 + wn * 64 + piece * 8;
+      if (MOM && !have_pivot) {
+        // (wave-uniform) first block of this wave: the pivot is tile pixel 0, which always exists, for every lane of a piece
+        const u32x4 p0 = *reinterpret_cast<const u32x4*>(otile + piece * 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { pv[2 * j] = __uint_as_float(p0[j] << 16); pv[2 * j + 1] = __uint_as_float(p0[j] & 0xffff0000u); }
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int pr = i * 8 + px;
         const u32x4 v = *reinterpret_cast<const u32x4*>(otile + pr * kOutRowB + piece * 16);
-        if (blk * 32 + pr < M) *reinterpret_cast<u32x4*>(ybase + (size_t)pr * N) = v;
+        const bool lv = blk * 32 + pr < M;
+        if (lv) *reinterpret_cast<u32x4*>(ybase + (size_t)pr * N) = v;
+        if (MOM) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float lo = __uint_as_float(v[j] << 16), hi = __uint_as_float(v[j] & 0xffff0000u);
+            const float dl = lv ? lo - pv[2 * j] : 0.f, dh = lv ? hi - pv[2 * j + 1] : 0.f;
+            s1[2 * j] += dl;     s2[2 * j] = fmaf(dl, dl, s2[2 * j]);
+            s1[2 * j + 1] += dh; s2[2 * j + 1] = fmaf(dh, dh, s2[2 * j + 1]);
+          }
+        }
       }
     }
+    have_pivot = true;
     if constexpr (DB) {
 #pragma unroll
       for (int ks = 0; ks < KC; ++ks) xf[ks] = xn[ks];
@@ -179,27 +184,25 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
         part[((size_t)row * N + n_slice0) * 4 + j] = 0.f;
       }
     }
-    // sum over the 32 pixel-lanes of each half (they share the pivot), then merge the workgroup's pixel-waves by
+    // sum over the 8 lanes that hold the same piece (they share the pivot), then merge the workgroup's pixel-waves by
     // re-basing them onto the first one's pivot (fixed order, through the LDS of the output tiles, which are done
     // with): one record per workgroup and channel
     __syncthreads();
     float* sums = reinterpret_cast<float*>(smem_raw + (size_t)NS * ROWB);          // [WM][NS][4]
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+    for (int i = 0; i < 8; ++i) {
+      float a = s1[i], b = s2[i];
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        float a = s1[t][i], b = s2[t][i];
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) {
-          a += __shfl_xor(a, off, kWave);
-          b += __shfl_xor(b, off, kWave);
-        }
-        if (r == 0) {
-          const int ch = wn * 64 + t * 32 + acc_channel(i, h);
-          float* rec = sums + ((size_t)wm * NS + ch) * 4;
-          rec[0] = a; rec[1] = b; rec[2] = pv[t][i]; rec[3] = (float)npix;
-        }
+      for (int off = 32; off >= 8; off >>= 1) {
+        a += __shfl_xor(a, off, kWave);
+        b += __shfl_xor(b, off, kWave);
       }
+      if (lane < 8) {
+        const int ch = wn * 64 + lane * 8 + i;
+        float* rec = sums + ((size_t)wm * NS + ch) * 4;
+        rec[0] = a; rec[1] = b; rec[2] = pv[i]; rec[3] = (float)npix;
+      }
+    }
     __syncthreads();
     float* dst = part + ((size_t)blockIdx.x * N + n_slice0) * 4;
     for (int ch = threadIdx.x; ch < NS; ch += NW * kWave) {
@@ -301,7 +304,10 @@ int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M
   switch (K) {
     case 64:  CALL(4) break;
     case 128: CALL(8) break;
-    case 256: CALL(16) break;
+    case 256:                               // conv1x1_geo() takes eight waves at K = 256: no four-wave instance
+      if (g.NW != 8) return MRLA_EUNSUPPORTED;
+      if (part) CALL_W(16, true, 8) else CALL_W(16, false, 8)
+      break;
     default: return MRLA_EUNSUPPORTED;
   }
 #undef CALL
