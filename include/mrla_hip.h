@@ -484,6 +484,22 @@ int mrla_conv1x1_add_supported(int m, int k, int n, int dtype);
 int mrla_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int dtype,
                          void* stream);
 
+/* The same for every shape mrla_conv1x1_fwd takes, and for the shortcut of a strided block (two ADDITIVE symbols: nothing
+ * above changes its arguments or its answers, MRLA_ABI_VERSION stays 5).
+ *   y viewed as [b, h, w_, n] with b*h*w_ == m (MRLA_EINVAL otherwise);
+ *   sh = sw = 1: addend is [m, n] like y;
+ *   otherwise:   addend is the COMPACT channels_last tensor [b, ceil(h/sh), ceil(w_/sw), n] -- the gradient of the subsample
+ *                x[:, :, ::sh, ::sw] in front of a strided 1x1 downsample convolution: output pixel (i, y, x) receives
+ *                addend[i, y/sh, x/sw] when y % sh == 0 and x % sw == 0, and nothing otherwise.  No full-size, mostly zero
+ *                tensor is built, filled or read.
+ * The wide form (mrla_conv1x1_add_supported) adds in fp32 before its one rounding, bit-equal to mrla_conv1x1_fwd_add on the
+ * scattered addend; the other forms add to the rounded product, bf16(bf16(x w^T) + addend), bit-equal to mrla_conv1x1_fwd
+ * followed by an elementwise bf16 add.  The addend may alias y when it is as large as y.  No moment records.
+ * mrla_conv1x1_addend_supported: 1, or MRLA_EUNSUPPORTED (shapes mrla_conv1x1_fwd does not take, m * max(n, k) * 2 >= 2^31). */
+int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype);
+int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int b, int h,
+                            int w_, int sh, int sw, int dtype, void* stream);
+
 /* Weight gradient of the same convolution (the backward of the reference's nn.Conv2d(kernel_size=1) call sites above,
  * which the reference leaves to cuDNN):   dw[n, k] = sum_m dy[m, n] * x[m, k]
  *   dy: [m, n] and x: [m, k] channels_last activations (bf16), dw: [n, k] (bf16, fp32 accumulation),

@@ -90,6 +90,8 @@ SIGNATURES = {
     "mrla_conv1x1_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "mrla_conv1x1_add_supported": [_I] * 4,
     "mrla_conv1x1_fwd_add": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "mrla_conv1x1_addend_supported": [_I] * 6,
+    "mrla_conv1x1_fwd_addend": [_P, _P, _P, _P] + [_I] * 9 + [_P],
     "mrla_conv1x1_wgrad_rows": [_I] * 4,
     "mrla_conv1x1_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],

@@ -700,6 +700,24 @@ int mrla_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void*
   return launch_conv1x1_wide(x, w, addend, y, nullptr, m, k, n, (hipStream_t)stream);
 }
 
+static bool bad_addend_geometry(int m, int b, int h, int w, int sh, int sw) {
+  return b <= 0 || h <= 0 || w <= 0 || sh <= 0 || sw <= 0 || (long long)b * h * w != (long long)m;
+}
+
+int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype) {
+  if (m <= 0 || k <= 0 || n <= 0 || sh <= 0 || sw <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  return conv1x1_addend_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
+}
+
+int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int b, int h,
+                            int w_, int sh, int sw, int dtype, void* stream) {
+  if (!x || !w || !addend || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || bad_addend_geometry(m, b, h, w_, sh, sw))
+    return MRLA_EINVAL;
+  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  return launch_conv1x1_addend(x, w, addend, y, m, k, n, b, h, w_, sh, sw, (hipStream_t)stream);
+}
+
 int mrla_conv1x1_wgrad_rows(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;

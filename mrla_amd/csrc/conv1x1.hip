@@ -21,9 +21,12 @@
 //     channels of 4 pixel rows of every block back from the tile, so 8 (sum, sum of squares, pivot) triples per lane
 //     cover the wave's 64 channels (in the accumulator layout, one triple per accumulator register = 96 registers, the
 //     K = 256 instance spilled); they are reduced across lanes and pixel-waves once at the end of the kernel and written
-//     as one partial row per workgroup.
+//     as one partial row per workgroup;
+//   * the input-gradient use with the shortcut's gradient (conv1x1_fwd_addend_kernel, no moments): the store lane adds the
+//     addend's 16 bytes of the same pixel and channels to the piece it read back from the tile (conv1x1_addend.h).
 #include <algorithm>
 
+#include "conv1x1_addend.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -38,10 +41,11 @@ constexpr int kOutTileB = 32 * kOutRowB;
 // channel of accumulator register `reg` inside its 32-channel tile, for lane half h
 __device__ __forceinline__ int acc_channel(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-template <int KS, bool MOM, int NW>
-__global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
-    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, bf16_t* __restrict__ Y, float* __restrict__ part,
-    int M, int N, int NS, int WN, int rows_total) {
+template <int KS, bool MOM, int NW, bool ADD>
+__device__ __forceinline__ void conv1x1_fwd_body(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, bf16_t* Y, float* __restrict__ part,
+    int M, int N, int NS, int WN, int rows_total, const bf16_t* A, const AddendGeo& ag) {
+  static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
   constexpr int K = KS * 16;
   constexpr int ROWB = K * 2 + 16;                   // padded LDS row of W, bytes
   constexpr int KC = KS < 16 ? KS : 16;              // k-steps whose X fragments are in registers at a time
@@ -95,6 +99,17 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+    // the addend pieces of the four pixel rows this lane stores (A may alias Y: a lane reads exactly the bytes it overwrites)
+    u32x4 av[ADD ? 4 : 1];
+    if (ADD) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      const auto rsA = addend_rsrc(A, ag, N);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        av[i] = __builtin_amdgcn_raw_buffer_load_b128(
+            rsA, addend_offset(ag, blk * 32 + i * 8 + (lane >> 3), M, N, n_slice0 + wn * 64 + (lane & 7) * 8), 0, 0);
+#endif
+    }
 #pragma unroll 1
     for (int kc = 0; kc < NCH; ++kc) {             // (not unrolled: the chunks' fragments must not be live together)
       if (kc > 0) load_x(xf, blk, kc);
@@ -153,7 +168,8 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int pr = i * 8 + px;
-        const u32x4 v = *reinterpret_cast<const u32x4*>(otile + pr * kOutRowB + piece * 16);
+        u32x4 v = *reinterpret_cast<const u32x4*>(otile + pr * kOutRowB + piece * 16);
+        if (ADD) v = addend_add8(v, av[i]);
         const bool lv = blk * 32 + pr < M;
         if (lv) *reinterpret_cast<u32x4*>(ybase + (size_t)pr * N) = v;
         if (MOM) {
@@ -220,6 +236,22 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
       dst[ch * 4 + 0] = S1; dst[ch * 4 + 1] = S2; dst[ch * 4 + 2] = P; dst[ch * 4 + 3] = n;
     }
   }
+}
+
+template <int KS, bool MOM, int NW>
+__global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, bf16_t* __restrict__ Y, float* __restrict__ part,
+    int M, int N, int NS, int WN, int rows_total) {
+  conv1x1_fwd_body<KS, MOM, NW, false>(X, W, Y, part, M, N, NS, WN, rows_total, nullptr, AddendGeo());
+}
+
+// y = bf16(bf16(x w^T) + addend).  A kernel name of its own: tests/test_kernel_resources_cpu.py keys the instances above by
+// <KS, MOM, NW>, and these are held to the same bounds by tests/test_shortcut_addend_cpu.py.
+template <int KS, int NW>
+__global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_addend_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, const bf16_t* A, bf16_t* Y, int M, int N, int NS, int WN,
+    AddendGeo ag) {
+  conv1x1_fwd_body<KS, false, NW, true>(X, W, Y, nullptr, M, N, NS, WN, 0, A, ag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -312,6 +344,46 @@ int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M
   }
 #undef CALL
 #undef CALL_M
+#undef CALL_W
+  return hip_status(hipGetLastError());
+}
+
+int conv1x1_addend_supported(int M, int K, int N) {
+  if ((size_t)M * std::max(N, K) * 2 >= (size_t)1 << 31) return 0;      // (also keeps every pixel index exact in fp32)
+  GemmGeo g;
+  return conv1x1_wide_rows(M, K, N) > 0 || conv1x1_geo(&g, M, K, N) || conv1x1_kstream_supported(M, K, N);
+}
+
+// The same dispatch as launch_conv1x1_fwd, with the addend (conv1x1_addend.h; sh = sw = 1: as large as y).  The wide form
+// adds in fp32 before its one rounding (mrla_conv1x1_fwd_add); the narrow and the K-streaming form add to the rounded output.
+int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h, int wd,
+                          int sh, int sw, hipStream_t st) {
+  if (!conv1x1_addend_supported(M, K, N)) return MRLA_EUNSUPPORTED;
+  if (conv1x1_wide_rows(M, K, N) > 0)
+    return sh * sw == 1 ? launch_conv1x1_wide(x, w, addend, y, nullptr, M, K, N, st)
+                        : launch_conv1x1_wide_sparse(x, w, addend, y, M, K, N, b, h, wd, sh, sw, st);
+  GemmGeo g;
+  if (!conv1x1_geo(&g, M, K, N)) return launch_conv1x1_kstream_addend(x, w, addend, y, M, K, N, b, h, wd, sh, sw, st);
+  const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
+  const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
+#define CALL_W(KS, NWV)                                                                                               \
+  {                                                                                                                   \
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_fwd_addend_kernel<KS, NWV>), g.lds) != hipSuccess)            \
+      return MRLA_EHIP;                                                                                               \
+    hipLaunchKernelGGL((conv1x1_fwd_addend_kernel<KS, NWV>), grid, block, g.lds, st, (const bf16_t*)x, (const bf16_t*)w, \
+                       (const bf16_t*)addend, (bf16_t*)y, M, N, g.NS, g.WN, ag);                                      \
+  }
+#define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
+  switch (K) {
+    case 64:  CALL(4) break;
+    case 128: CALL(8) break;
+    case 256:
+      if (g.NW != 8) return MRLA_EUNSUPPORTED;
+      CALL_W(16, 8)
+      break;
+    default: return MRLA_EUNSUPPORTED;
+  }
+#undef CALL
 #undef CALL_W
   return hip_status(hipGetLastError());
 }

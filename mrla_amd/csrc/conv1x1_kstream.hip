@@ -24,6 +24,7 @@
 // K <= 256 siblings they are bound by the matrix pipe as much as by memory; MIOpen's kernels reach 25 - 30 % of it.
 #include <algorithm>
 
+#include "conv1x1_addend.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -72,11 +73,25 @@ __device__ __forceinline__ int ks_oswz(int row) { return row & 7; }            /
 // record of this pixel tile per channel (MRLA_GEMM_MOMENTS: sum (y - p), sum (y - p)^2, p, count; y = the ROUNDED outputs,
 // p = the tile's first pixel) -- thread (srow, chunk) keeps eight channels over its rows, the RPI row-threads of a chunk are
 // folded through LDS in a fixed order once the tile has been read.
-template <int TM, int TN, bool MOM>
-__device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned lds0, bf16_t* __restrict__ Y,
-                                              float* __restrict__ mom_part, int M, int N, int m0, int n0, int tile) {
+// ADD (the input-gradient use, never with MOM): the thread that stores a 16-byte piece adds the addend's 16 bytes of the same
+// pixel and channels to the staged bf16 values (conv1x1_addend.h: full-size or the compact gradient of a strided subsample;
+// A may alias Y -- a thread reads exactly the bytes it overwrites).  Its TM / RPI addend loads are issued together, ahead
+// of the LDS reads: the accumulators are dead here, and a dependent load in front of every store would put the load
+// latency into the tile epilogue once per row.
+template <int TM, int TN, bool MOM, bool ADD>
+__device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned lds0, bf16_t* Y,
+                                              float* __restrict__ mom_part, int M, int N, int m0, int n0, int tile,
+                                              const bf16_t* A, const AddendGeo& ag) {
+  static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
   constexpr int CPR = TN / 8, RPI = (kKsWaves * kWave) / CPR;
   const int srow = threadIdx.x / CPR, chunk = threadIdx.x % CPR;
+  u32x4 av[ADD ? TM / RPI : 1];
+  if (ADD) {
+    const auto rsA = addend_rsrc(A, ag, N);
+#pragma unroll
+    for (int i = 0; i < TM / RPI; ++i)
+      av[i] = __builtin_amdgcn_raw_buffer_load_b128(rsA, addend_offset(ag, m0 + srow + RPI * i, M, N, n0 + chunk * 8), 0, 0);
+  }
   float piv[8], s1[8], s2[8];
   if (MOM) {
     u32x4 pv;
@@ -96,6 +111,7 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
     u32x4 v;
     ks_read16(v, lds0 + row * (TN * 2) + ((chunk ^ ks_oswz(row)) << 4));
     ks_fence<0>(v, true);
+    if (ADD) v = addend_add8(v, av[i]);
     if (m0 + row < M) {
       *reinterpret_cast<u32x4*>(Y + (size_t)(m0 + row) * N + n0 + chunk * 8) = v;
       if (MOM) {
@@ -133,12 +149,13 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
   }
 }
 
-template <int WN, int PB, bool MOM>
+template <int WN, int PB, bool MOM, bool ADD>
 __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(const bf16_t* __restrict__ X,
                                                                              const bf16_t* __restrict__ W,
-                                                                             bf16_t* __restrict__ Y,
+                                                                             bf16_t* Y,
                                                                              float* __restrict__ mom_part, int M, int N,
-                                                                             int K, int tiles_m, int groups_n) {
+                                                                             int K, int tiles_m, int groups_n,
+                                                                             const bf16_t* A, AddendGeo ag) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef KsGeo<WN, PB> G;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -289,7 +306,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<G::TM, G::TN, MOM>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile);
+  ks_store_tile<G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
 #endif
 }
 
@@ -307,12 +324,13 @@ struct Ks256 {
   static constexpr int kLds = ST * SB;                  // 128 KB: also exactly the bf16 output tile
 };
 
-template <bool MOM>
+template <bool MOM, bool ADD>
 __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(const bf16_t* __restrict__ X,
                                                                                const bf16_t* __restrict__ W,
-                                                                               bf16_t* __restrict__ Y,
+                                                                               bf16_t* Y,
                                                                                float* __restrict__ mom_part, int M, int N,
-                                                                               int K, int tiles_m, int groups_n) {
+                                                                               int K, int tiles_m, int groups_n,
+                                                                               const bf16_t* A, AddendGeo ag) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Ks256 G;
   constexpr int PB = G::PB;
@@ -463,7 +481,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<G::TM, G::TN, MOM>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile);
+  ks_store_tile<G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
 #endif
 }
 
@@ -497,24 +515,45 @@ KsPlan ks_plan(int M, int K, int N) {
   return p;
 }
 
-template <int WN, int PB, bool MOM>
-int ks_launch_m(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
+template <int WN, int PB, bool MOM, bool ADD>
+int ks_launch_m(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
+                const void* a, const AddendGeo& ag) {
   typedef KsGeo<WN, PB> G;
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_kernel<WN, PB, MOM>), G::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_kstream_kernel<WN, PB, MOM>), dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
-                     G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n);
+  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
+  hipLaunchKernelGGL((conv1x1_kstream_kernel<WN, PB, MOM, ADD>), dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
+                     G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n,
+                     (const bf16_t*)a, ag);
   return hip_status(hipGetLastError());
 }
+// a != null: the addend form (never with records)
 template <int WN, int PB>
-int ks_launch(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
-  return part ? ks_launch_m<WN, PB, true>(p, x, w, y, part, M, K, N, st) : ks_launch_m<WN, PB, false>(p, x, w, y, part, M, K, N, st);
+int ks_launch(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
+              const void* a, const AddendGeo& ag) {
+  if (a) return ks_launch_m<WN, PB, false, true>(p, x, w, y, nullptr, M, K, N, st, a, ag);
+  return part ? ks_launch_m<WN, PB, true, false>(p, x, w, y, part, M, K, N, st, a, ag)
+              : ks_launch_m<WN, PB, false, false>(p, x, w, y, part, M, K, N, st, a, ag);
 }
-template <bool MOM>
-int ks_launch256(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_kernel<MOM>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL(conv1x1_kstream256_kernel<MOM>, dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
-                     Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n);
+template <bool MOM, bool ADD>
+int ks_launch256(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
+                 const void* a, const AddendGeo& ag) {
+  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
+  hipLaunchKernelGGL((conv1x1_kstream256_kernel<MOM, ADD>), dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
+                     Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n,
+                     (const bf16_t*)a, ag);
   return hip_status(hipGetLastError());
+}
+
+int ks_dispatch(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st, const void* a,
+                const AddendGeo& ag) {
+  const KsPlan p = ks_plan(M, K, N);
+  if (!p.wn) return MRLA_EUNSUPPORTED;
+  if (p.big) {
+    if (a) return ks_launch256<false, true>(p, x, w, y, nullptr, M, K, N, st, a, ag);
+    return part ? ks_launch256<true, false>(p, x, w, y, part, M, K, N, st, a, ag)
+                : ks_launch256<false, false>(p, x, w, y, part, M, K, N, st, a, ag);
+  }
+  if (p.wn == 4) return p.pb == 2 ? ks_launch<4, 2>(p, x, w, y, part, M, K, N, st, a, ag) : ks_launch<4, 1>(p, x, w, y, part, M, K, N, st, a, ag);
+  return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, st, a, ag) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, st, a, ag);
 }
 
 }  // namespace
@@ -525,11 +564,13 @@ int conv1x1_kstream_stages(int M, int K, int N) { return ks_plan(M, K, N).big ? 
 
 // part != null: moment records [conv1x1_kstream_rows()][N][MRLA_GEMM_MOMENTS] of the rounded outputs (one row per pixel tile)
 int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
-  const KsPlan p = ks_plan(M, K, N);
-  if (!p.wn) return MRLA_EUNSUPPORTED;
-  if (p.big) return part ? ks_launch256<true>(p, x, w, y, part, M, K, N, st) : ks_launch256<false>(p, x, w, y, part, M, K, N, st);
-  if (p.wn == 4) return p.pb == 2 ? ks_launch<4, 2>(p, x, w, y, part, M, K, N, st) : ks_launch<4, 1>(p, x, w, y, part, M, K, N, st);
-  return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, st) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, st);
+  return ks_dispatch(x, w, y, part, M, K, N, st, nullptr, AddendGeo());
+}
+
+// y = bf16(bf16(x w^T) + addend); addend: [M, N], or with sh * sw > 1 the compact [b, ceil(h/sh), ceil(w/sw), N] (M = b*h*w)
+int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
+                                  int wd, int sh, int sw, hipStream_t st) {
+  return ks_dispatch(x, w, y, nullptr, M, K, N, st, addend, make_addend_geo(b, h, wd, sh, sw));
 }
 
 }  // namespace mrla

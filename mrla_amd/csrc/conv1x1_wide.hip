@@ -17,11 +17,14 @@
 //     pixel row r sits at chunk position c ^ f(r): conflict-free for the 16-lane groups of ds_read_b128);
 //   * workgroup ids are re-mapped so that the channel groups of one pixel range run side by side on one XCD (L2 hits);
 //   * the 32 x 256 bf16 output tile is assembled in LDS and leaves as whole 512-byte rows; with `A` the DMA drops the
-//     addend tile into that staging buffer first and the epilogue adds in fp32 before the one rounding;
+//     addend tile into that staging buffer first and the epilogue adds in fp32 before the one rounding; SP: the addend
+//     is the compact gradient of a strided subsample (conv1x1_addend.h) -- a lane's DMA offset is then computed from its
+//     pixel, and a pixel without an addend is fetched at the out-of-bounds offset (zeros, no traffic);
 //   * one barrier per pixel block; LDS traffic of the pipeline is inline asm with explicit waits (the compiler would put
 //     `s_waitcnt vmcnt(0)` in front of every LDS access it sees after an LDS-DMA load).
 #include <algorithm>
 
+#include "conv1x1_addend.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -71,12 +74,14 @@ template <int CPR>
 __device__ __forceinline__ int cw_swz(int row) { return CPR >= 16 ? (row & 15) : ((row >> 1) & 7); }
 __device__ __forceinline__ int cw_oswz(int row) { return row & 7; }
 
-template <int KS, bool MOM, bool ADD>
+template <int KS, bool MOM, bool ADD, bool SP>
 __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf16_t* __restrict__ X,
                                                                        const bf16_t* __restrict__ W,
                                                                        const bf16_t* __restrict__ A, bf16_t* __restrict__ Y,
                                                                        float* __restrict__ part, int M, int N,
-                                                                       int units_per_wg, int nsplits, int rows_total) {
+                                                                       int units_per_wg, int nsplits, int rows_total,
+                                                                       AddendGeo ag) {
+  static_assert(ADD || !SP, "a compact addend is an addend");
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef CwGeo<KS, ADD> G;
   constexpr int K = G::K, CPR = K / 8, UST = G::UST;
@@ -106,7 +111,7 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
   // ---- DMA plan ----
   const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)((size_t)M * K * 2), MRLA_CW_FLAGS);
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ADD ? A : X), 0,
-                                                     ADD ? (int)((size_t)M * N * 2) : 0, MRLA_CW_FLAGS);
+                                                     ADD ? (int)((size_t)(SP ? ag.rows : M) * N * 2) : 0, MRLA_CW_FLAGS);
   unsigned voffX[G::NIX], voffA[ADD ? G::NIA : 1];
   constexpr bool kIdleWaves = G::XB / 1024 < kCwWaves;          // K = 64: four real X instructions, waves 4-7 issue a dummy
   const bool idle = kIdleWaves && wave >= G::XB / 1024;
@@ -120,12 +125,14 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
 #pragma unroll
     for (int i = 0; i < G::NIA; ++i) {
       const int u = wave + kCwWaves * i, row = u * 2 + lane / 32, cp = lane % 32;
-      voffA[i] = (unsigned)(((size_t)u_begin * 32 + row) * N * 2 + cg * (kCwTN * 2) + ((cp ^ cw_oswz(row)) << 4));
+      // SP: the position inside the pixel's row only; the row is found per unit
+      voffA[i] = (unsigned)((SP ? (size_t)0 : ((size_t)u_begin * 32 + row) * N * 2) + cg * (kCwTN * 2) + ((cp ^ cw_oswz(row)) << 4));
     }
   }
   const unsigned advX = 32u * K * 2, advA = 32u * (unsigned)N * 2;
   int issued = 0;
   auto issue = [&](int slot) {
+    const int pix0 = (u_begin + issued) * 32;                    // first pixel of the unit being fetched
     const unsigned kill = issued++ < nun ? 0u : 0x80000000u;     // past the range: out of bounds, no memory traffic
 #pragma unroll
     for (int i = 0; i < G::NIX; ++i) {
@@ -133,12 +140,21 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void_ptr)dst, 16, voffX[i] | kill, 0, 0, 0);
       voffX[i] += advX;
     }
-    if (ADD) {
+    if (ADD && !SP) {
 #pragma unroll
       for (int i = 0; i < G::NIA; ++i) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_ptr)(smem_raw + G::kXRing + slot * kOutB + (wave + kCwWaves * i) * 1024),
                                                  16, voffA[i] | kill, 0, 0, 0);
         voffA[i] += advA;
+      }
+    }
+    if (ADD && SP) {
+#pragma unroll
+      for (int i = 0; i < G::NIA; ++i) {
+        const int arow = addend_row(ag, pix0 + (wave + kCwWaves * i) * 2 + lane / 32, M);
+        const unsigned vo = arow < 0 ? 0x80000000u : (unsigned)arow * ((unsigned)N * 2) + voffA[i];
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_void_ptr)(smem_raw + G::kXRing + slot * kOutB + (wave + kCwWaves * i) * 1024),
+                                                 16, vo | kill, 0, 0, 0);
       }
     }
   };
@@ -356,14 +372,15 @@ CwPlan cw_plan(int M, int K, int N) {
   return p;
 }
 
-template <int KS, bool MOM, bool ADD>
-int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void* y, float* part, int M, int N, hipStream_t st) {
+template <int KS, bool MOM, bool ADD, bool SP = false>
+int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void* y, float* part, int M, int N, hipStream_t st,
+              const AddendGeo& ag = AddendGeo()) {
   typedef CwGeo<KS, ADD> G;
   static_assert(G::kLds <= 160 * 1024, "LDS");
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD>), dim3((p.groups * p.splits + 7) / 8 * 8), dim3(kCwWaves * kWave),
+  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
+  hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD, SP>), dim3((p.groups * p.splits + 7) / 8 * 8), dim3(kCwWaves * kWave),
                      G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)a, (bf16_t*)y, part, M, N,
-                     p.units_per_wg, p.splits, p.rows);
+                     p.units_per_wg, p.splits, p.rows, ag);
   return hip_status(hipGetLastError());
 }
 
@@ -405,6 +422,20 @@ int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* 
     default: return MRLA_EUNSUPPORTED;
   }
 #undef MRLA_CW_CALL
+}
+
+// y = x w^T + the compact addend [b, ceil(h/sh), ceil(w/sw), N] of a strided subsample (see conv1x1_addend.h); M = b*h*w
+int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
+                               int wd, int sh, int sw, hipStream_t st) {
+  const CwPlan p = cw_plan(M, K, N);
+  if (!p.groups) return MRLA_EUNSUPPORTED;
+  const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
+  switch (K) {
+    case 64: return cw_launch<4, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
+    case 128: return cw_launch<8, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
+    case 256: return cw_launch<16, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
+    default: return MRLA_EUNSUPPORTED;
+  }
 }
 
 }  // namespace mrla

@@ -173,6 +173,10 @@ int nhwc_images_per_group(int B, int C, int W);
 int conv1x1_rows(int M, int K, int N);
 int conv1x1_plan(int M, int K, int N, int add, int* out);
 int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st);
+// ... + addend (the shortcut's gradient in the input-gradient use): [M, N], or compact [b, ceil(h/sh), ceil(w/sw), N]
+int conv1x1_addend_supported(int M, int K, int N);
+int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h, int wd,
+                          int sh, int sw, hipStream_t st);
 // stem_pool_nhwc.hip -- maxpool3x3/s2/p1(relu(bn(x))) without the intermediate tensor (channels_last, C % 64 == 0)
 int bn_pool_rows(int B, int C, int H, int W);
 int launch_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int B, int C, int H, int W,
@@ -186,11 +190,15 @@ int conv1x1_wide_rows(int M, int K, int N);
 int conv1x1_wide_plan(int M, int K, int N, int add, int* out);
 int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* y, float* part, int M, int K, int N,
                         hipStream_t st);
+int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
+                               int wd, int sh, int sw, hipStream_t st);      // compact addend of a strided subsample
 // conv1x1_kstream.hip -- the same product for wide reductions (K >= 512): both operands streamed through LDS; the tile copy-out takes the BatchNorm moment records as well
 int conv1x1_kstream_supported(int M, int K, int N);
 int conv1x1_kstream_stages(int M, int K, int N);      // LDS stages of the kernel the planner picks (3, or 4: the 256 x 256 tile)
 int conv1x1_kstream_rows(int M, int K, int N);        // rows of the moment records (one per pixel tile)
 int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st);
+int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
+                                  int wd, int sh, int sw, hipStream_t st);
 // conv1x1_wgrad.hip -- its weight gradient dW[n,k] = sum_m dY[m,n] X[m,k] as a split-M MFMA GEMM (bf16)
 int conv1x1_wgrad_rows(int M, int K, int N);
 int conv1x1_wgrad_plan(int M, int K, int N, int* out);

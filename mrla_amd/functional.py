@@ -59,6 +59,12 @@ LEAN = False      # True: the fused training tail does not store x_t where the l
 #                   what the forward one saves, profiles/r06_notes.md section 3) -- switch it on for the memory.
 
 
+SHORTCUT_ADDEND = True   # conv1's input-gradient GEMM takes the block's shortcut gradient as its addend in every kernel form
+#                          and straight from the compact gradient of a strided downsample (mrla_conv1x1_fwd_addend).  False:
+#                          only the wide form adds a full-size one (mrla_conv1x1_fwd_add); a torch add, and a zero-fill +
+#                          scatter for the strided blocks, do the rest -- the same values, kept for A/B runs and tests.
+
+
 def _seq():
     return SEQUENCES and TIMER is None
 
@@ -1407,10 +1413,16 @@ class _Conv1x1Fn(torch.autograd.Function):
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, want_moments, passthrough=False, w16=None, w16t=None):
+    def forward(ctx, x, w, want_moments, passthrough=False, w16=None, w16t=None, sub=None):
         """w16 / w16t: bf16 working copies [n, k] / [k, n] of an fp32 master weight `w` (WeightBank); the weight gradient
-        is then returned in the master's dtype straight from the reduction kernel."""
+        is then returned in the master's dtype straight from the reduction kernel.
+        sub = (sh, sw), with passthrough: the third output is x[:, :, ::sh, ::sw] (dense channels_last) instead of x -- the
+        input of the block's strided downsample convolution.  Its gradient then comes back COMPACT, and the input-gradient
+        GEMM reads it in place (mrla_conv1x1_fwd_addend) instead of a zero-filled full-size tensor it was scattered into.
+        It is an ordinary output of this node: a second consumer, a hook or torch.autograd.grad on it see the true
+        gradient of the subsampled tensor, whichever path the backward then takes."""
         ctx.set_materialize_grads(False)       # (the moment rows carry no gradient; the shortcut's may be absent)
+        ctx.sub = tuple(sub) if (passthrough and sub is not None) else None
         b, k, h, wd = x.shape
         n = w.shape[0]
         m = b * h * wd
@@ -1436,6 +1448,8 @@ class _Conv1x1Fn(torch.autograd.Function):
         if part is None:
             part = torch.empty(0, device=dev)
         ctx.mark_non_differentiable(part)
+        if ctx.sub is not None:
+            return y, part, x[:, :, ::ctx.sub[0], ::ctx.sub[1]].contiguous(memory_format=_CL)
         if passthrough:             # x itself as a third output: its gradient (the shortcut's) comes back to backward()
             return y, part, x
         return y, part
@@ -1444,8 +1458,12 @@ class _Conv1x1Fn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy, _dpart=None, d_through=None):
         x, w, w16t = ctx.saved_tensors
+        sub = ctx.sub
+        sh, sw = sub if sub is not None else (1, 1)
         if dy is None:             # only the shortcut carried a gradient
-            return (d_through if ctx.needs_input_grad[0] else None), None, None, None, None, None
+            if d_through is not None and sub is not None:
+                d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
+            return (d_through if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
         dy = dy.contiguous(memory_format=_CL)
         n, k = w.shape
         b, _, h, wd = x.shape
@@ -1462,9 +1480,18 @@ class _Conv1x1Fn(torch.autograd.Function):
         if need_x and same and lib.mrla_conv1x1_rows(m, n, k, dt) >= 0:
             gx = torch.empty_like(x)
             wt = w16t if w16t is not None else w.t().contiguous()
-            if d_through is not None and lib.mrla_conv1x1_add_supported(m, n, k, dt) == 1:
-                # ... + the shortcut's gradient in the GEMM epilogue (fp32 sum, one rounding) instead of a separate
+            if d_through is not None and SHORTCUT_ADDEND and lib.mrla_conv1x1_addend_supported(m, n, k, sh, sw, dt) == 1:
+                # ... + the shortcut's gradient inside the GEMM, whichever kernel form takes the shape, and from the compact
+                # gradient of a strided block's subsample as it is (no zero-fill, no scatter, a quarter of the addend bytes)
+                _call("mrla_conv1x1_bwd_data", (dy.numel() + gx.numel() + d_through.numel()) * x.element_size(), _ptr(dy),
+                      _ptr(wt), _ptr(d_through), _ptr(gx), m, n, k, b, h, wd, sh, sw, dt, _stream(),
+                      entry="mrla_conv1x1_fwd_addend")
+                d_through = None
+            elif d_through is not None and lib.mrla_conv1x1_add_supported(m, n, k, dt) == 1:
+                # ... + the shortcut's gradient in the wide GEMM's epilogue (fp32 sum, one rounding) instead of a separate
                 # accumulation pass over the block input's gradient
+                if sub is not None:
+                    d_through, sub = _scatter_subsample(d_through, x.shape, sh, sw, _CL), None
                 _call("mrla_conv1x1_bwd_data", (dy.numel() + 2 * gx.numel()) * x.element_size(), _ptr(dy), _ptr(wt),
                       _ptr(d_through), _ptr(gx), m, n, k, dt, _stream(), entry="mrla_conv1x1_fwd_add")
                 d_through = None
@@ -1488,16 +1515,27 @@ class _Conv1x1Fn(torch.autograd.Function):
             gx = gx2 if need_x else gx
             gw = gw2.reshape(n, k) if need_w else gw
         if d_through is not None and ctx.needs_input_grad[0]:
+            # what no GEMM took: a shape or dtype off the HIP path, SHORTCUT_ADDEND off and a form other than the wide one
+            if sub is not None:
+                d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
             gx = gx + d_through
         if gw is not None:          # the weight's own dtype, shape AND strides (autograd's / DDP's gradient layout contract)
             gw = _grad_like(gw.to(ctx.wdtype), ctx.wshape, ctx.wstride)
-        return gx, gw, None, None, None, None
+        return gx, gw, None, None, None, None, None
+
+
+def _scatter_subsample(g, shape, sh, sw, fmt):
+    """The gradient of x[:, :, ::sh, ::sw] in x's shape and memory format: zeros, `g` at the sampled pixels."""
+    dx = torch.empty(shape, dtype=g.dtype, device=g.device, memory_format=fmt).zero_()
+    dx[:, :, ::sh, ::sw] = g
+    return dx
 
 
 class _SubsampleFn(torch.autograd.Function):
     """x[:, :, ::sh, ::sw] as a dense channels_last tensor, with a backward that stays channels_last: zeros everywhere, the
     incoming gradient at the sampled pixels (autograd's own slice backward answers in NCHW memory, which would cost the
-    consumer -- conv1's input-gradient GEMM takes it as the shortcut's gradient -- a full-size layout conversion)."""
+    consumer a full-size layout conversion).  A bottleneck's shortcut does not come through here when conv1 runs on the
+    GEMMs: there the subsample is an output of conv1's node (_Conv1x1Fn, sub=...), whose backward needs no full-size tensor."""
 
     @staticmethod
     def forward(ctx, x, sh, sw):
@@ -1508,10 +1546,7 @@ class _SubsampleFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        sh, sw = ctx.s
-        dx = torch.empty(ctx.shape, dtype=g.dtype, device=g.device, memory_format=ctx.fmt).zero_()
-        dx[:, :, ::sh, ::sw] = g
-        return dx, None, None
+        return _scatter_subsample(g, ctx.shape, ctx.s[0], ctx.s[1], ctx.fmt), None, None
 
 
 def _strided_1x1(conv):
@@ -1534,7 +1569,7 @@ def conv1x1_applies(conv, x, strided=False):
     b, k, h, w = x.shape
     if k != conv.in_channels:
         return False
-    if strided:
+    if strided and strided != "pre":                       # ("pre": `x` is the subsampled input already)
         h, w = (h + conv.stride[0] - 1) // conv.stride[0], (w + conv.stride[1] - 1) // conv.stride[1]
     lib, m, n = L.load(), b * h * w, conv.out_channels
     if lib.mrla_conv1x1_rows(m, k, n, L.BF16) >= 0:
@@ -1542,22 +1577,41 @@ def conv1x1_applies(conv, x, strided=False):
     return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, L.BF16) > 0
 
 
-def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False):
+def shortcut_subsample(downsample, x):
+    """(sh, sw) when `downsample` is the strided 1x1 convolution + BatchNorm of a stage's first block
+    (resnet_mrla_light.py:196-199) and runs on the GEMMs for the block input `x`, else None.  The block then asks conv1 for
+    the subsampled input (conv_bn_act(..., passthrough=True, subsample=...)) and hands it on with presampled=True."""
+    if not (isinstance(downsample, torch.nn.Sequential) and len(downsample) == 2 and _strided_1x1(downsample[0])):
+        return None
+    if not (torch.is_tensor(x) and x.dim() == 4 and conv1x1_applies(downsample[0], x, True)):
+        return None
+    return tuple(downsample[0].stride)
+
+
+def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=None, presampled=False):
     """relu?(bn(conv(x))) -- resnet_mrla_light.py:93-94,100-101.  Eligible 1x1 convolutions run on the HIP GEMM, whose
     epilogue hands the train-mode BatchNorm its statistics (the moments pass over the output disappears); everything
     else is `bn_act(conv(x), ...)` with the stock convolution.
     passthrough=True returns (result, x'), x' being x routed through the convolution's autograd node: a consumer that
     uses x' as the block's shortcut (resnet_mrla_light.py:91,110-114) gets the shortcut gradient added inside the
-    convolution's input-gradient GEMM instead of by a separate accumulation pass."""
+    convolution's input-gradient GEMM instead of by a separate accumulation pass.
+    subsample=(sh, sw), with passthrough: x' is x[:, :, ::sh, ::sw] routed the same way -- the input of the block's strided
+    downsample convolution (shortcut_subsample), whose input gradient then reaches the GEMM compact instead of scattered
+    into a zero-filled tensor of x's size.  presampled=True: `conv` is that strided 1x1 convolution and `x` the already
+    subsampled input."""
+    def second(t):                  # the second result where the convolution's own node does not produce it
+        return _SubsampleFn.apply(t, subsample[0], subsample[1]) if subsample is not None else t
+
     fused_bn = (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats)
     # A strided 1x1 convolution is the stride-1 one on the subsampled input: one strided copy (a quarter of the pixels), then
     # the same GEMMs -- forward with the BatchNorm statistics in its epilogue, input gradient, weight gradient.  Not for speed
     # alone: MIOpen's input gradient of exactly these convolutions is right when launched eagerly and garbage from the second
     # replay of a HIP graph on (every mode: immediate, find, deterministic; scripts/miopen_bwd_graph_probe.py,
     # profiles/r05_notes.md section 2) -- with them on the GEMMs the whole step replays correctly.
-    strided = _strided_1x1(conv) and not passthrough and x.dim() == 4 and conv1x1_applies(conv, x, True)
+    strided = (_strided_1x1(conv) and not passthrough and x.dim() == 4
+               and conv1x1_applies(conv, x, "pre" if presampled else True))
     if strided or conv1x1_applies(conv, x):
-        if strided:
+        if strided and not presampled:
             x = _SubsampleFn.apply(x, conv.stride[0], conv.stride[1])
         wt, w16, w16t = conv.weight, None, None
         if wt.dtype != x.dtype:
@@ -1568,11 +1622,13 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False):
             else:
                 wt = wt.to(x.dtype)                  # what autocast does for the stock convolution (differentiable)
         if passthrough and torch.is_grad_enabled() and x.requires_grad:
-            y, part, through = _Conv1x1Fn.apply(x, wt, bool(fused_bn and bn.training), True, w16, w16t)
+            y, part, through = _Conv1x1Fn.apply(x, wt, bool(fused_bn and bn.training), True, w16, w16t, subsample)
             return bn_act(y, bn, relu, defer, pre_moments=part if part.numel() else None), through
         y, part = _Conv1x1Fn.apply(x, wt, bool(fused_bn and bn.training), False, w16, w16t)
         out = bn_act(y, bn, relu, defer, pre_moments=part if part.numel() else None)
-        return (out, x) if passthrough else out
+        return (out, second(x)) if passthrough else out
+    if presampled:                  # (not reached from the models: shortcut_subsample() asked conv1x1_applies first)
+        return bn_act(torch.nn.functional.conv2d(x, conv.weight), bn, relu, defer)
     if _strided_1x1(conv) and not passthrough and x.dim() == 4 and x.is_cuda:
         # every other dtype / layout (resnet/train.py itself trains in fp32, :397-409): still the stride-1 convolution on the
         # subsampled input -- a plain GEMM for MIOpen, whose input gradient needs no zero-fill + scatter; the zero-fill and
@@ -1580,4 +1636,4 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False):
         xs = _SubsampleFn.apply(x, conv.stride[0], conv.stride[1])
         return bn_act(torch.nn.functional.conv2d(xs, conv.weight), bn, relu, defer)
     out = bn_act(conv(x), bn, relu, defer)
-    return (out, x) if passthrough else out
+    return (out, second(x)) if passthrough else out

@@ -81,8 +81,10 @@ class _BottleneckTrunk(nn.Module):
         # 1x1 convolutions: HIP MFMA GEMM with the BatchNorm statistics in its epilogue when eligible (bf16, channels_last).
         # The block input's second consumer -- the shortcut itself, or the downsample branch -- takes it through conv1's
         # autograd node, so that its gradient is added in the epilogue of conv1's input-gradient GEMM instead of by
-        # autograd's accumulation pass.
-        out, identity = F_.conv_bn_act(x, self.conv1, self.bn1, relu=True, passthrough=True)
+        # autograd's accumulation pass.  In front of a strided 1x1 downsample, conv1's node hands out the subsampled input
+        # itself, and gets its gradient back compact: no zero-filled tensor of x's size is built for the GEMM to read.
+        sub = F_.shortcut_subsample(self.downsample, x)
+        out, identity = F_.conv_bn_act(x, self.conv1, self.bn1, relu=True, passthrough=True, subsample=sub)
         out = F_.bn_act(self.conv2(out), self.bn2, relu=True)
         if self.se is not None or self.eca is not None:     # channel attention reads bn3's output: nothing to defer
             defer_bn3 = False
@@ -99,7 +101,7 @@ class _BottleneckTrunk(nn.Module):
         if self.downsample is not None:
             ds = self.downsample
             if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d):
-                identity = F_.conv_bn_act(identity, ds[0], ds[1], relu=False)
+                identity = F_.conv_bn_act(identity, ds[0], ds[1], relu=False, presampled=sub is not None)
             else:
                 identity = ds(identity)
         return out, identity
