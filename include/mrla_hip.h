@@ -75,6 +75,9 @@ enum { MRLA_BN_NONE = 0, MRLA_BN_TRAIN = 1, MRLA_BN_EVAL = 2 };
  *           Where the strips do not fill the chip either, the ROWS of an image are cut into ranges as well (a range re-fetches
  *           its two halo rows; the backward apply pass re-computes one row of dU): the same three queries count those
  *           ranges too, nothing else changes for a caller.  mrla_tuning_row_ranges() was added.
+ *           Additive since (no bump): every mrla_conv1x1_* entry point takes MRLA_F16 wherever it takes MRLA_BF16, with the
+ *           same answers for the same (m, k, n) -- callers that pass MRLA_BF16 see no change -- and
+ *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh.
  * A consumer compares mrla_abi_version() (what the loaded library was built from) against this constant before its
  * first call. */
 #define MRLA_ABI_VERSION 5
@@ -456,15 +459,16 @@ int mrla_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, const 
  * The 1x1 stride-1 convolutions in front of those BatchNorms as an MFMA GEMM whose epilogue takes the BatchNorm
  * statistics (first half; reference call sites resnet/models/resnet_mrla_light.py:93-94
  * `conv1 -> bn1` and :100-101 `conv3 -> bn3`, both nn.Conv2d(kernel_size=1, stride=1, bias=False)).
- *   y[m, n] = sum_k x[m, k] * w[n, k]        x: channels_last activation viewed as [m = b*h*w, k = c_in] (bf16),
- *                                            w: the conv weight [n = c_out, k] (bf16), y: [m, n] (bf16, fp32 accumulate)
+ *   y[m, n] = sum_k x[m, k] * w[n, k]        x: channels_last activation viewed as [m = b*h*w, k = c_in],
+ *                                            w: the conv weight [n = c_out, k], y: [m, n]; all three of `dtype`, MRLA_BF16
+ *                                            or MRLA_F16 (fp32 accumulate, one rounding to nearest even, overflow to +-inf)
  *   mom_part[row, n, 0..3] [opt] = moment record (MRLA_GEMM_MOMENTS) over the row's pixels of the ROUNDED outputs --
  *   the statistics mrla_bn_plane_moments would read back from y, taken about a per-row pivot so that the one-pass
  *   variance stays well conditioned when |mean| >> sigma; hand it to mrla_bn_stats_fwd_rows.
  * Three kernel families behind it: k in {64, 128, 256} with n % 64 == 0 (weights resident on chip; one record row per
  * workgroup row), and k >= 512 with k % 32 == 0, n % 128 == 0 (both operands streamed; one record row per pixel tile).
  * mom_part may be NULL (no statistics wanted: the input-gradient use, inference).
- * MRLA_EUNSUPPORTED for other shapes and for dtypes other than MRLA_BF16: the caller keeps its stock convolution there.
+ * MRLA_EUNSUPPORTED for other shapes and for dtypes other than MRLA_BF16 / MRLA_F16: the caller keeps its stock convolution there.
  * (The input gradient dX = dY * W is the same entry point with w^T.) */
 int mrla_conv1x1_rows(int m, int k, int n, int dtype);      /* rows of mom_part (> 0: every supported shape writes
                                                                records), or a negative code (unsupported shape) */
@@ -493,8 +497,8 @@ int mrla_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void*
  *                addend[i, y/sh, x/sw] when y % sh == 0 and x % sw == 0, and nothing otherwise.  No full-size, mostly zero
  *                tensor is built, filled or read.
  * The wide form (mrla_conv1x1_add_supported) adds in fp32 before its one rounding, bit-equal to mrla_conv1x1_fwd_add on the
- * scattered addend; the other forms add to the rounded product, bf16(bf16(x w^T) + addend), bit-equal to mrla_conv1x1_fwd
- * followed by an elementwise bf16 add.  The addend may alias y when it is as large as y.  No moment records.
+ * scattered addend; the other forms add to the rounded product, T(T(x w^T) + addend) in the element type T, bit-equal to
+ * mrla_conv1x1_fwd followed by an elementwise add in that type.  The addend may alias y when it is as large as y.  No moment records.
  * mrla_conv1x1_addend_supported: 1, or MRLA_EUNSUPPORTED (shapes mrla_conv1x1_fwd does not take, m * max(n, k) * 2 >= 2^31). */
 int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype);
 int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int b, int h,
@@ -502,28 +506,31 @@ int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, vo
 
 /* Weight gradient of the same convolution (the backward of the reference's nn.Conv2d(kernel_size=1) call sites above,
  * which the reference leaves to cuDNN):   dw[n, k] = sum_m dy[m, n] * x[m, k]
- *   dy: [m, n] and x: [m, k] channels_last activations (bf16), dw: [n, k] (bf16, fp32 accumulation),
+ *   dy: [m, n] and x: [m, k] channels_last activations (of `dtype`: MRLA_BF16 or MRLA_F16), dw: [n, k] (fp32 accumulation),
  *   part: fp32 workspace [rows, n, k] with rows = mrla_conv1x1_wgrad_rows(m, k, n, dtype): the per-workgroup partial
  *   tiles of the split over m, summed in a fixed order by a second kernel (no atomics, no memset of dw).
- * MRLA_EUNSUPPORTED unless n % 64 == 0, k % 64 == 0, dtype MRLA_BF16 and m * max(n, k) * 2 < 2^31. */
+ * MRLA_EUNSUPPORTED unless n % 64 == 0, k % 64 == 0, dtype MRLA_BF16 or MRLA_F16 and m * max(n, k) * 2 < 2^31. */
 int mrla_conv1x1_wgrad_rows(int m, int k, int n, int dtype);      /* rows of part (> 0), or a negative code */
 /* Host-side query, `out` is a HOST array of 6 ints: 32-pixel chunks per workgroup, LDS stages, tile n, tile k,
  * splits (= mrla_conv1x1_wgrad_rows()), output tiles. */
 int mrla_conv1x1_wgrad_plan(int m, int k, int n, int dtype, int* out);
-/* dw_dtype: MRLA_BF16 (the autocast copy's gradient, as the stock backward produces it) or MRLA_F32 (the fp32 master
+/* dw_dtype: `dtype` itself (the autocast copy's gradient, as the stock backward produces it) or MRLA_F32 (the fp32 master
  * weight's gradient directly: the sum over the partial tiles is fp32 anyway, and the cast kernel autograd would append
- * disappears). */
+ * disappears).  A 16-bit dw_dtype other than dtype (MRLA_BF16 with MRLA_F16 or the reverse) is MRLA_EINVAL. */
 int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                        void* stream);
 
-/* The bf16 working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
+/* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input
  * gradient): replaces what torch.autocast does in front of nn.Conv2d (resnet/train.py runs fp32; the bf16 configuration of
  * BASELINE.json casts each weight per forward).
- *   table: DEVICE array of `entries` x 4 int64: { src fp32 [n, k] pointer, dst bf16 [n, k] pointer,
- *          dst_t bf16 [k, n] pointer or 0, (n << 32) | k };  n % 64 == 0, k % 64 == 0.
- *   max_tiles: the largest (n / 64) * (k / 64) over the entries. */
+ *   table: DEVICE array of `entries` x 4 int64: { src fp32 [n, k] pointer, dst [n, k] pointer,
+ *          dst_t [k, n] pointer or 0, (n << 32) | k };  n % 64 == 0, k % 64 == 0.
+ *   max_tiles: the largest (n / 64) * (k / 64) over the entries.
+ * mrla_weight_bank_refresh writes bf16 copies; mrla_weight_bank_refresh_dt (additive, ABI 5) writes copies of `dtype`,
+ * MRLA_BF16 or MRLA_F16 (round to nearest even, overflow to +-inf, as a torch cast), MRLA_EUNSUPPORTED for MRLA_F32. */
 int mrla_weight_bank_refresh(const void* table, int entries, int max_tiles, void* stream);
+int mrla_weight_bank_refresh_dt(const void* table, int entries, int max_tiles, int dtype, void* stream);
 
 /* out[n] = sum over rows of in[rows, n] (fixed order, double accumulation). */
 int mrla_reduce_rows(const float* in, float* out, int rows, int n, void* stream);

@@ -95,6 +95,7 @@ SIGNATURES = {
     "mrla_conv1x1_wgrad_rows": [_I] * 4,
     "mrla_conv1x1_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],
+    "mrla_weight_bank_refresh_dt": [_P, _I, _I, _I, _P],
     "mrla_reduce_rows": [_P, _P, _I, _I, _P],
     "mrla_reduce_rows2": [_P, _P, _I, _I, _P, _P, _I, _I, _P],
     # sequence entry points (ABI 4): one call = the static launch sequence of a tail and direction
@@ -149,17 +150,17 @@ def check(rc, what):
         raise MrlaHipError(f"{what}: {_ERR.get(rc, 'error')} (code {rc})")
 
 
-def conv1x1_plan(m, k, n, addend=False):
+def conv1x1_plan(m, k, n, addend=False, dtype=None):
     """(pixel blocks per workgroup, pipeline depth, workgroups, moment rows) of mrla_conv1x1_fwd[_add], or None."""
     out = (ctypes.c_int * 4)()
-    rc = load().mrla_conv1x1_plan(m, k, n, BF16, int(addend), ctypes.cast(out, ctypes.c_void_p))
+    rc = load().mrla_conv1x1_plan(m, k, n, BF16 if dtype is None else dtype, int(addend), ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 
-def conv1x1_wgrad_plan(m, k, n):
+def conv1x1_wgrad_plan(m, k, n, dtype=None):
     """(chunks per workgroup, LDS stages, tile n, tile k, splits, tiles) of mrla_conv1x1_wgrad, or None."""
     out = (ctypes.c_int * 6)()
-    rc = load().mrla_conv1x1_wgrad_plan(m, k, n, BF16, ctypes.cast(out, ctypes.c_void_p))
+    rc = load().mrla_conv1x1_wgrad_plan(m, k, n, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 

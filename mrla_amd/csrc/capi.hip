@@ -665,39 +665,39 @@ int mrla_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, const 
 
 int mrla_conv1x1_rows(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_rows(m, k, n);
 }
 
 int mrla_conv1x1_plan(int m, int k, int n, int dtype, int addend, int* out) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || !out) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_plan(m, k, n, addend, out);
 }
 
 int mrla_conv1x1_wgrad_plan(int m, int k, int n, int dtype, int* out) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || !out) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_wgrad_plan(m, k, n, out);
 }
 
 int mrla_conv1x1_fwd(const void* x, const void* w, void* y, float* mom_part, int m, int k, int n, int dtype, void* stream) {
   if (!x || !w || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
-  return launch_conv1x1_fwd(x, w, y, mom_part, m, k, n, (hipStream_t)stream);
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_conv1x1_fwd(x, w, y, mom_part, m, k, n, dtype, (hipStream_t)stream);
 }
 
 int mrla_conv1x1_add_supported(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_wide_rows(m, k, n) > 0 ? 1 : MRLA_EUNSUPPORTED;
 }
 
 int mrla_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int dtype,
                          void* stream) {
   if (!x || !w || !addend || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
-  return launch_conv1x1_wide(x, w, addend, y, nullptr, m, k, n, (hipStream_t)stream);
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_conv1x1_wide(x, w, addend, y, nullptr, m, k, n, dtype, (hipStream_t)stream);
 }
 
 static bool bad_addend_geometry(int m, int b, int h, int w, int sh, int sw) {
@@ -706,7 +706,7 @@ static bool bad_addend_geometry(int m, int b, int h, int w, int sh, int sw) {
 
 int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || sh <= 0 || sw <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_addend_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
 }
 
@@ -714,27 +714,35 @@ int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, vo
                             int w_, int sh, int sw, int dtype, void* stream) {
   if (!x || !w || !addend || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || bad_addend_geometry(m, b, h, w_, sh, sw))
     return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
-  return launch_conv1x1_addend(x, w, addend, y, m, k, n, b, h, w_, sh, sw, (hipStream_t)stream);
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_conv1x1_addend(x, w, addend, y, m, k, n, b, h, w_, sh, sw, dtype, (hipStream_t)stream);
 }
 
 int mrla_conv1x1_wgrad_rows(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return conv1x1_wgrad_rows(m, k, n);
 }
 
 int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                        void* stream) {
   if (!dy || !x || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16) return MRLA_EUNSUPPORTED;
-  return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, (hipStream_t)stream);
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  // dw is of the operands' type or fp32: a bf16 gradient of fp16 operands (or the reverse) is a caller's mistake
+  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
 int mrla_weight_bank_refresh(const void* table, int entries, int max_tiles, void* stream) {
   if (!table || entries <= 0 || max_tiles <= 0) return MRLA_EINVAL;
-  return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, (hipStream_t)stream);
+  return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, MRLA_BF16, (hipStream_t)stream);
+}
+
+int mrla_weight_bank_refresh_dt(const void* table, int entries, int max_tiles, int dtype, void* stream) {
+  if (!table || entries <= 0 || max_tiles <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, dtype, (hipStream_t)stream);
 }
 
 int mrla_reduce_rows(const float* in, float* out, int rows, int n, void* stream) {

@@ -1,4 +1,4 @@
-// 1x1 stride-1 convolution of a channels_last bf16 activation as an MFMA GEMM with a BatchNorm-statistics epilogue:
+// 1x1 stride-1 convolution of a channels_last bf16 or fp16 activation as an MFMA GEMM with a BatchNorm-statistics epilogue:
 //   Y[M, N] = X[M, K] * W[N, K]^T      (M = b*h*w pixels, K = in-channels, N = out-channels; both operands K-contiguous)
 //   part[row, n, 0..3] = per-workgroup moment record of the bf16-ROUNDED outputs of channel n (MRLA_GEMM_MOMENTS):
 //                        sum (y - p), sum (y - p)^2, the pivot p (a first output of the channel), pixel count
@@ -32,8 +32,7 @@
 
 namespace mrla {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef c1_f32x16 f32x16;
 
 constexpr int kOutRowB = 64 * 2 + 16;               // padded row of the per-wave output tile (64 channels of one pixel)
 constexpr int kOutTileB = 32 * kOutRowB;
@@ -41,10 +40,12 @@ constexpr int kOutTileB = 32 * kOutRowB;
 // channel of accumulator register `reg` inside its 32-channel tile, for lane half h
 __device__ __forceinline__ int acc_channel(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-template <int KS, bool MOM, int NW, bool ADD>
+template <typename T, int KS, bool MOM, int NW, bool ADD>
 __device__ __forceinline__ void conv1x1_fwd_body(
-    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, bf16_t* Y, float* __restrict__ part,
-    int M, int N, int NS, int WN, int rows_total, const bf16_t* A, const AddendGeo& ag) {
+    const T* __restrict__ X, const T* __restrict__ W, T* Y, float* __restrict__ part,
+    int M, int N, int NS, int WN, int rows_total, const T* A, const AddendGeo& ag) {
+  typedef Elem16<T> E;
+  typedef typename E::x8 x8;
   static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
   constexpr int K = KS * 16;
   constexpr int ROWB = K * 2 + 16;                   // padded LDS row of W, bytes
@@ -119,23 +120,16 @@ __device__ __forceinline__ void conv1x1_fwd_body(
 #pragma unroll
         for (int ks = 0; ks < KC; ++ks) {
           const u32x4 wf = *reinterpret_cast<const u32x4*>(wrow + ks * 32);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf),
-                                                           __builtin_bit_cast(bf16x8, xf[ks]), acc[t], 0, 0, 0);
+          E::mfma(acc[t], __builtin_bit_cast(x8, wf), __builtin_bit_cast(x8, xf[ks]));
         }
       }
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      // round to bf16 (pairs of neighbouring channels)
+      // round to the element type (pairs of neighbouring channels)
       unsigned p[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-        bf16x2 pr;
-        pr[0] = from_f<bf16_t>(acc[t][2 * i]);
-        pr[1] = from_f<bf16_t>(acc[t][2 * i + 1]);
-        p[i] = __builtin_bit_cast(unsigned, pr);
-      }
+      for (int i = 0; i < 8; ++i) p[i] = E::pack(acc[t][2 * i], acc[t][2 * i + 1]);
       // lane half 0 holds channels {0-3, 8-11, 16-19, 24-27} of its pixel, half 1 the other four groups; after the
       // swaps half 0 holds {0-7, 16-23} and half 1 {8-15, 24-31}: two 16-byte pieces per lane
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -158,24 +152,24 @@ __device__ __forceinline__ void conv1x1_fwd_body(
     // those of the rounded values the lane stores (4 pixel rows of its 8 channels per block; rows past M: neither)
     {
       const int px = lane >> 3, piece = lane & 7;
-      bf16_t* ybase = Y + (size_t)blk * 32 * N + n_slice0 + wn * 64 + piece * 8;
+      T* ybase = Y + (size_t)blk * 32 * N + n_slice0 + wn * 64 + piece * 8;
       if (MOM && !have_pivot) {
         // (wave-uniform) first block of this wave: the pivot is tile pixel 0, which always exists, for every lane of a piece
         const u32x4 p0 = *reinterpret_cast<const u32x4*>(otile + piece * 16);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { pv[2 * j] = __uint_as_float(p0[j] << 16); pv[2 * j + 1] = __uint_as_float(p0[j] & 0xffff0000u); }
+        for (int j = 0; j < 4; ++j) { pv[2 * j] = E::lo(p0[j]); pv[2 * j + 1] = E::hi(p0[j]); }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int pr = i * 8 + px;
         u32x4 v = *reinterpret_cast<const u32x4*>(otile + pr * kOutRowB + piece * 16);
-        if (ADD) v = addend_add8(v, av[i]);
+        if (ADD) v = addend_add8<T>(v, av[i]);
         const bool lv = blk * 32 + pr < M;
         if (lv) *reinterpret_cast<u32x4*>(ybase + (size_t)pr * N) = v;
         if (MOM) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float lo = __uint_as_float(v[j] << 16), hi = __uint_as_float(v[j] & 0xffff0000u);
+            const float lo = E::lo(v[j]), hi = E::hi(v[j]);
             const float dl = lv ? lo - pv[2 * j] : 0.f, dh = lv ? hi - pv[2 * j + 1] : 0.f;
             s1[2 * j] += dl;     s2[2 * j] = fmaf(dl, dl, s2[2 * j]);
             s1[2 * j + 1] += dh; s2[2 * j + 1] = fmaf(dh, dh, s2[2 * j + 1]);
@@ -242,7 +236,15 @@ template <int KS, bool MOM, int NW>
 __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, bf16_t* __restrict__ Y, float* __restrict__ part,
     int M, int N, int NS, int WN, int rows_total) {
-  conv1x1_fwd_body<KS, MOM, NW, false>(X, W, Y, part, M, N, NS, WN, rows_total, nullptr, AddendGeo());
+  conv1x1_fwd_body<bf16_t, KS, MOM, NW, false>(X, W, Y, part, M, N, NS, WN, rows_total, nullptr, AddendGeo());
+}
+// The fp16 instances: the same body, under a name of their own (the tests that read the compiler's resource report key the
+// bf16 instances by the template lists of the names above).
+template <int KS, bool MOM, int NW>
+__global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_f16_kernel(
+    const f16_t* __restrict__ X, const f16_t* __restrict__ W, f16_t* __restrict__ Y, float* __restrict__ part,
+    int M, int N, int NS, int WN, int rows_total) {
+  conv1x1_fwd_body<f16_t, KS, MOM, NW, false>(X, W, Y, part, M, N, NS, WN, rows_total, nullptr, AddendGeo());
 }
 
 // y = bf16(bf16(x w^T) + addend).  A kernel name of its own: tests/test_kernel_resources_cpu.py keys the instances above by
@@ -251,7 +253,13 @@ template <int KS, int NW>
 __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_addend_kernel(
     const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, const bf16_t* A, bf16_t* Y, int M, int N, int NS, int WN,
     AddendGeo ag) {
-  conv1x1_fwd_body<KS, false, NW, true>(X, W, Y, nullptr, M, N, NS, WN, 0, A, ag);
+  conv1x1_fwd_body<bf16_t, KS, false, NW, true>(X, W, Y, nullptr, M, N, NS, WN, 0, A, ag);
+}
+template <int KS, int NW>
+__global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_f16_addend_kernel(
+    const f16_t* __restrict__ X, const f16_t* __restrict__ W, const f16_t* A, f16_t* Y, int M, int N, int NS, int WN,
+    AddendGeo ag) {
+  conv1x1_fwd_body<f16_t, KS, false, NW, true>(X, W, Y, nullptr, M, N, NS, WN, 0, A, ag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -316,20 +324,25 @@ int conv1x1_plan(int M, int K, int N, int add, int* out) {
   return MRLA_OK;
 }
 
-int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
-  if (conv1x1_wide_rows(M, K, N) > 0) return launch_conv1x1_wide(x, w, nullptr, y, part, M, K, N, st);
+int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st) {
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (conv1x1_wide_rows(M, K, N) > 0) return launch_conv1x1_wide(x, w, nullptr, y, part, M, K, N, dtype, st);
   GemmGeo g;
   if (!conv1x1_geo(&g, M, K, N)) {
     if (!conv1x1_kstream_supported(M, K, N)) return MRLA_EUNSUPPORTED;
-    return launch_conv1x1_kstream(x, w, y, part, M, K, N, st);
+    return launch_conv1x1_kstream(x, w, y, part, M, K, N, dtype, st);
   }
   const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
+#define CALL_T(KERNEL, T, KS, MO, NWV)                                                                             \
+  {                                                                                                                  \
+    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, MO, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;        \
+    hipLaunchKernelGGL((KERNEL<KS, MO, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, (T*)y, part, M, N,    \
+                       g.NS, g.WN, g.rows);                                                                          \
+  }
 #define CALL_W(KS, MO, NWV)                                                                                          \
   {                                                                                                                  \
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_fwd_kernel<KS, MO, NWV>), g.lds) != hipSuccess)              \
-      return MRLA_EHIP;                                                                                              \
-    hipLaunchKernelGGL((conv1x1_fwd_kernel<KS, MO, NWV>), grid, block, g.lds, st, (const bf16_t*)x, (const bf16_t*)w, \
-                       (bf16_t*)y, part, M, N, g.NS, g.WN, g.rows);                                                  \
+    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_kernel, f16_t, KS, MO, NWV)                                        \
+    else CALL_T(conv1x1_fwd_kernel, bf16_t, KS, MO, NWV)                                                             \
   }
 #define CALL_M(KS, MO) { if (g.NW == 4) CALL_W(KS, MO, 4) else CALL_W(KS, MO, 8) }
 #define CALL(KS) { if (part) CALL_M(KS, true) else CALL_M(KS, false) }
@@ -345,6 +358,7 @@ int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M
 #undef CALL
 #undef CALL_M
 #undef CALL_W
+#undef CALL_T
   return hip_status(hipGetLastError());
 }
 
@@ -357,21 +371,26 @@ int conv1x1_addend_supported(int M, int K, int N) {
 // The same dispatch as launch_conv1x1_fwd, with the addend (conv1x1_addend.h; sh = sw = 1: as large as y).  The wide form
 // adds in fp32 before its one rounding (mrla_conv1x1_fwd_add); the narrow and the K-streaming form add to the rounded output.
 int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h, int wd,
-                          int sh, int sw, hipStream_t st) {
+                          int sh, int sw, int dtype, hipStream_t st) {
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   if (!conv1x1_addend_supported(M, K, N)) return MRLA_EUNSUPPORTED;
   if (conv1x1_wide_rows(M, K, N) > 0)
-    return sh * sw == 1 ? launch_conv1x1_wide(x, w, addend, y, nullptr, M, K, N, st)
-                        : launch_conv1x1_wide_sparse(x, w, addend, y, M, K, N, b, h, wd, sh, sw, st);
+    return sh * sw == 1 ? launch_conv1x1_wide(x, w, addend, y, nullptr, M, K, N, dtype, st)
+                        : launch_conv1x1_wide_sparse(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
   GemmGeo g;
-  if (!conv1x1_geo(&g, M, K, N)) return launch_conv1x1_kstream_addend(x, w, addend, y, M, K, N, b, h, wd, sh, sw, st);
+  if (!conv1x1_geo(&g, M, K, N)) return launch_conv1x1_kstream_addend(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
   const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
   const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
+#define CALL_T(KERNEL, T, KS, NWV)                                                                                    \
+  {                                                                                                                   \
+    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;             \
+    hipLaunchKernelGGL((KERNEL<KS, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, (const T*)addend, (T*)y,   \
+                       M, N, g.NS, g.WN, ag);                                                                         \
+  }
 #define CALL_W(KS, NWV)                                                                                               \
   {                                                                                                                   \
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_fwd_addend_kernel<KS, NWV>), g.lds) != hipSuccess)            \
-      return MRLA_EHIP;                                                                                               \
-    hipLaunchKernelGGL((conv1x1_fwd_addend_kernel<KS, NWV>), grid, block, g.lds, st, (const bf16_t*)x, (const bf16_t*)w, \
-                       (const bf16_t*)addend, (bf16_t*)y, M, N, g.NS, g.WN, ag);                                      \
+    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_addend_kernel, f16_t, KS, NWV)                                      \
+    else CALL_T(conv1x1_fwd_addend_kernel, bf16_t, KS, NWV)                                                           \
   }
 #define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
   switch (K) {
@@ -385,6 +404,7 @@ int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void
   }
 #undef CALL
 #undef CALL_W
+#undef CALL_T
   return hip_status(hipGetLastError());
 }
 

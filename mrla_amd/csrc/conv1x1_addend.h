@@ -4,6 +4,7 @@
 // belongs to output pixel (i, yc*sh, xc*sw); the other output pixels have no addend.  The kernels read it in place of the
 // zero-filled full-size tensor a scatter would build.
 #pragma once
+#include "conv1x1_elem.h"
 #include "mrla_device.h"
 
 namespace mrla {
@@ -51,26 +52,23 @@ __device__ __forceinline__ int addend_row(const AddendGeo& g, int p, int M) {
 // Descriptor and byte offset for reading addend pieces with bounds-checked buffer loads: a pixel without addend is read at
 // an out-of-bounds offset, which returns zeros and moves nothing -- no branch around the load, so a thread's loads issue
 // back to back.  (rows * N * 2 < 2^31: conv1x1_addend_supported.)
-__device__ __forceinline__ auto addend_rsrc(const bf16_t* A, const AddendGeo& g, int N) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(A), 0, (int)((size_t)g.rows * N * 2), 0x00020000);
+template <typename T>
+__device__ __forceinline__ auto addend_rsrc(const T* A, const AddendGeo& g, int N) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A), 0, (int)((size_t)g.rows * N * 2), 0x00020000);
 }
 __device__ __forceinline__ unsigned addend_offset(const AddendGeo& g, int p, int M, int N, int col) {
   const int row = addend_row(g, p, M);
   return row < 0 ? 0x80000000u : ((unsigned)row * (unsigned)N + (unsigned)col) * 2u;
 }
 
-// bf16(float(a) + float(b)) per element of eight packed bf16: what a separate elementwise add of the stored GEMM output
-// and the addend produces (two roundings: the GEMM's and this one)
+// T(float(a) + float(b)) per element of eight packed 16-bit elements: what a separate elementwise add of the stored GEMM
+// output and the addend produces (two roundings: the GEMM's and this one)
+template <typename T>
 __device__ __forceinline__ u32x4 addend_add8(const u32x4& a, const u32x4& b) {
+  typedef Elem16<T> E;
   u32x4 o;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-    bf16x2 pr;
-    pr[0] = from_f<bf16_t>(__uint_as_float(a[j] << 16) + __uint_as_float(b[j] << 16));
-    pr[1] = from_f<bf16_t>(__uint_as_float(a[j] & 0xffff0000u) + __uint_as_float(b[j] & 0xffff0000u));
-    o[j] = __builtin_bit_cast(unsigned, pr);
-  }
+  for (int j = 0; j < 4; ++j) o[j] = E::pack(E::lo(a[j]) + E::lo(b[j]), E::hi(a[j]) + E::hi(b[j]));
   return o;
 }
 

@@ -1,5 +1,5 @@
 // 1x1 stride-1 convolution with a WIDE REDUCTION (K = 512 .. 2048 input channels) as a K-streaming MFMA GEMM:
-//   Y[M, N] = X[M, K] * W[N, K]^T        bf16 in / out, fp32 accumulate;  M = b*h*w pixels, K % 32 == 0, N % 128 == 0
+//   Y[M, N] = X[M, K] * W[N, K]^T        bf16 or fp16 in / out, fp32 accumulate;  M = b*h*w pixels, K % 32 == 0, N % 128 == 0
 // Reference: conv1 of the bottlenecks of stages 2-4 (resnet/models/resnet_mrla_light.py:93: 512 / 1024 / 2048 -> width),
 // conv3 of stage 4 (:100: 512 -> 2048) and, with the operands swapped by the caller (x = dY, w = W^T), the input
 // gradients of conv3 everywhere but stage 1 and of conv1 in stage 4.
@@ -31,8 +31,7 @@
 namespace mrla {
 namespace {
 
-typedef __bf16 ks_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float ks_f32x16 __attribute__((ext_vector_type(16)));
+typedef c1_f32x16 ks_f32x16;
 
 #define MRLA_KS_FLAGS 0x00020000          /* raw buffer descriptor word 3 (as nhwc_rows.h) */
 constexpr int kKsWaves = 8;
@@ -69,19 +68,20 @@ __device__ __forceinline__ int ks_swz(int row) { return (row >> 2) & 3; }      /
 __device__ __forceinline__ int ks_oswz(int row) { return row & 7; }            // chunk swizzle of an output-tile row
 
 
-// Copy the staged bf16 tile [TM][TN] (16-byte chunks swizzled by ks_oswz) out as whole rows; MOM: also the BatchNorm moment
+// Copy the staged tile [TM][TN] (16-byte chunks swizzled by ks_oswz) out as whole rows; MOM: also the BatchNorm moment
 // record of this pixel tile per channel (MRLA_GEMM_MOMENTS: sum (y - p), sum (y - p)^2, p, count; y = the ROUNDED outputs,
 // p = the tile's first pixel) -- thread (srow, chunk) keeps eight channels over its rows, the RPI row-threads of a chunk are
 // folded through LDS in a fixed order once the tile has been read.
 // ADD (the input-gradient use, never with MOM): the thread that stores a 16-byte piece adds the addend's 16 bytes of the same
-// pixel and channels to the staged bf16 values (conv1x1_addend.h: full-size or the compact gradient of a strided subsample;
+// pixel and channels to the staged values (conv1x1_addend.h: full-size or the compact gradient of a strided subsample;
 // A may alias Y -- a thread reads exactly the bytes it overwrites).  Its TM / RPI addend loads are issued together, ahead
 // of the LDS reads: the accumulators are dead here, and a dependent load in front of every store would put the load
 // latency into the tile epilogue once per row.
-template <int TM, int TN, bool MOM, bool ADD>
-__device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned lds0, bf16_t* Y,
+template <typename T, int TM, int TN, bool MOM, bool ADD>
+__device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned lds0, T* Y,
                                               float* __restrict__ mom_part, int M, int N, int m0, int n0, int tile,
-                                              const bf16_t* A, const AddendGeo& ag) {
+                                              const T* A, const AddendGeo& ag) {
+  typedef Elem16<T> E;
   static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
   constexpr int CPR = TN / 8, RPI = (kKsWaves * kWave) / CPR;
   const int srow = threadIdx.x / CPR, chunk = threadIdx.x % CPR;
@@ -100,8 +100,8 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned wv = j == 0 ? pv.x : j == 1 ? pv.y : j == 2 ? pv.z : pv.w;
-      piv[2 * j] = __uint_as_float(wv << 16);
-      piv[2 * j + 1] = __uint_as_float(wv & 0xffff0000u);
+      piv[2 * j] = E::lo(wv);
+      piv[2 * j + 1] = E::hi(wv);
       s1[2 * j] = s1[2 * j + 1] = s2[2 * j] = s2[2 * j + 1] = 0.f;
     }
   }
@@ -111,14 +111,14 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
     u32x4 v;
     ks_read16(v, lds0 + row * (TN * 2) + ((chunk ^ ks_oswz(row)) << 4));
     ks_fence<0>(v, true);
-    if (ADD) v = addend_add8(v, av[i]);
+    if (ADD) v = addend_add8<T>(v, av[i]);
     if (m0 + row < M) {
       *reinterpret_cast<u32x4*>(Y + (size_t)(m0 + row) * N + n0 + chunk * 8) = v;
       if (MOM) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const unsigned wv = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-          const float d0 = __uint_as_float(wv << 16) - piv[2 * j], d1 = __uint_as_float(wv & 0xffff0000u) - piv[2 * j + 1];
+          const float d0 = E::lo(wv) - piv[2 * j], d1 = E::hi(wv) - piv[2 * j + 1];
           s1[2 * j] += d0; s2[2 * j] = fmaf(d0, d0, s2[2 * j]);
           s1[2 * j + 1] += d1; s2[2 * j + 1] = fmaf(d1, d1, s2[2 * j + 1]);
         }
@@ -149,14 +149,13 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
   }
 }
 
-template <int WN, int PB, bool MOM, bool ADD>
-__global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(const bf16_t* __restrict__ X,
-                                                                             const bf16_t* __restrict__ W,
-                                                                             bf16_t* Y,
-                                                                             float* __restrict__ mom_part, int M, int N,
-                                                                             int K, int tiles_m, int groups_n,
-                                                                             const bf16_t* A, AddendGeo ag) {
+template <typename T, int WN, int PB, bool MOM, bool ADD>
+__device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, const T* __restrict__ W, T* Y,
+                                                     float* __restrict__ mom_part, int M, int N, int K, int tiles_m,
+                                                     int groups_n, const T* A, const AddendGeo& ag) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  typedef Elem16<T> E;
+  typedef typename E::x8 ks_x8;
   typedef KsGeo<WN, PB> G;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & (kWave - 1);
@@ -173,8 +172,8 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
 
   // ---- DMA plan: instruction u = wave + 8*i covers stage rows 16u .. 16u+15 (4 lanes per 64-byte row);
   //      rows [0, TM) are X pixels, [TM, TM+TN) W channels, the rest does not exist (out-of-bounds offset: no traffic) ----
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
   unsigned voff[kKsNI];
   bool isw[kKsNI];
 #pragma unroll
@@ -252,8 +251,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
     for (int p = 0; p < PB; ++p)
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
-        acc[p][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ks_bf16x8, a[0][cb]),
-                                                             __builtin_bit_cast(ks_bf16x8, b[0][p]), acc[p][cb], 0, 0, 0);
+        E::mfma(acc[p][cb], __builtin_bit_cast(ks_x8, a[0][cb]), __builtin_bit_cast(ks_x8, b[0][p]));
     ks_fence<0>(a[1][0], true);
     ks_fence<0>(a[1][1], false);
 #pragma unroll
@@ -263,8 +261,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
     for (int p = 0; p < PB; ++p)
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
-        acc[p][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ks_bf16x8, a[1][cb]),
-                                                             __builtin_bit_cast(ks_bf16x8, b[1][p]), acc[p][cb], 0, 0, 0);
+        E::mfma(acc[p][cb], __builtin_bit_cast(ks_x8, a[1][cb]), __builtin_bit_cast(ks_x8, b[1][p]));
   }
   // the two dummy chunks issued past the end carry no data, but their LDS writes must be over before the tile is staged
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -281,13 +278,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
     for (int cb = 0; cb < 2; ++cb) {
       unsigned q[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-        bf16x2 pr;
-        pr[0] = from_f<bf16_t>(acc[p][cb][2 * i]);
-        pr[1] = from_f<bf16_t>(acc[p][cb][2 * i + 1]);
-        q[i] = __builtin_bit_cast(unsigned, pr);
-      }
+      for (int i = 0; i < 8; ++i) q[i] = E::pack(acc[p][cb][2 * i], acc[p][cb][2 * i + 1]);
       // half 0 holds channels {0-3, 8-11, 16-19, 24-27}, half 1 the other four groups; after the swaps half 0 holds
       // {0-7, 16-23} and half 1 {8-15, 24-31}: two 16-byte pieces per lane
 #pragma unroll
@@ -306,8 +297,28 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
+  ks_store_tile<T, G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
 #endif
+}
+
+template <int WN, int PB, bool MOM, bool ADD>
+__global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(const bf16_t* __restrict__ X,
+                                                                             const bf16_t* __restrict__ W,
+                                                                             bf16_t* Y,
+                                                                             float* __restrict__ mom_part, int M, int N,
+                                                                             int K, int tiles_m, int groups_n,
+                                                                             const bf16_t* A, AddendGeo ag) {
+  conv1x1_kstream_body<bf16_t, WN, PB, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
+}
+// the fp16 instances (a name of their own: see conv1x1_fwd_f16_kernel)
+template <int WN, int PB, bool MOM, bool ADD>
+__global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_f16_kernel(const f16_t* __restrict__ X,
+                                                                                 const f16_t* __restrict__ W,
+                                                                                 f16_t* Y,
+                                                                                 float* __restrict__ mom_part, int M, int N,
+                                                                                 int K, int tiles_m, int groups_n,
+                                                                                 const f16_t* A, AddendGeo ag) {
+  conv1x1_kstream_body<f16_t, WN, PB, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -321,17 +332,16 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_kernel(con
 // ------------------------------------------------------------------------------------------------
 struct Ks256 {
   static constexpr int TM = 256, TN = 256, ROWS = TM + TN, SB = ROWS * 64, ST = 4, NI = 4, PB = 4;
-  static constexpr int kLds = ST * SB;                  // 128 KB: also exactly the bf16 output tile
+  static constexpr int kLds = ST * SB;                  // 128 KB: also exactly the 16-bit output tile
 };
 
-template <bool MOM, bool ADD>
-__global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(const bf16_t* __restrict__ X,
-                                                                               const bf16_t* __restrict__ W,
-                                                                               bf16_t* Y,
-                                                                               float* __restrict__ mom_part, int M, int N,
-                                                                               int K, int tiles_m, int groups_n,
-                                                                               const bf16_t* A, AddendGeo ag) {
+template <typename T, bool MOM, bool ADD>
+__device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X, const T* __restrict__ W, T* Y,
+                                                        float* __restrict__ mom_part, int M, int N, int K, int tiles_m,
+                                                        int groups_n, const T* A, const AddendGeo& ag) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  typedef Elem16<T> E;
+  typedef typename E::x8 ks_x8;
   typedef Ks256 G;
   constexpr int PB = G::PB;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -346,8 +356,8 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(
   const int wn = wave & 3, wm = wave >> 2;
   const int nchunks = K / kKsKC;
 
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
   unsigned voff[G::NI];
 #pragma unroll
   for (int i = 0; i < G::NI; ++i) {       // instruction u = wave + 8*i: stage rows 16u .. 16u+15; i < 2: X pixels, else W channels
@@ -408,8 +418,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(
     for (int p = 0; p < PB; ++p)
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
-        acc[p][cb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(ks_bf16x8, fa[buf][cb]),
-                                                             __builtin_bit_cast(ks_bf16x8, fb[buf][p]), acc[p][cb], 0, 0, 0);
+        E::mfma(acc[p][cb], __builtin_bit_cast(ks_x8, fa[buf][cb]), __builtin_bit_cast(ks_x8, fb[buf][p]));
   };
 
   // chunks 0 .. 2 in flight, chunk 3 follows once chunk 0 is complete everywhere
@@ -458,13 +467,7 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(
     for (int cb = 0; cb < 2; ++cb) {
       unsigned q[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-        bf16x2 pr;
-        pr[0] = from_f<bf16_t>(acc[p][cb][2 * i]);
-        pr[1] = from_f<bf16_t>(acc[p][cb][2 * i + 1]);
-        q[i] = __builtin_bit_cast(unsigned, pr);
-      }
+      for (int i = 0; i < 8; ++i) q[i] = E::pack(acc[p][cb][2 * i], acc[p][cb][2 * i + 1]);
 #pragma unroll
       for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -481,8 +484,27 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
+  ks_store_tile<T, G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
 #endif
+}
+
+template <bool MOM, bool ADD>
+__global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_kernel(const bf16_t* __restrict__ X,
+                                                                               const bf16_t* __restrict__ W,
+                                                                               bf16_t* Y,
+                                                                               float* __restrict__ mom_part, int M, int N,
+                                                                               int K, int tiles_m, int groups_n,
+                                                                               const bf16_t* A, AddendGeo ag) {
+  conv1x1_kstream256_body<bf16_t, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
+}
+template <bool MOM, bool ADD>
+__global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_f16_kernel(const f16_t* __restrict__ X,
+                                                                                   const f16_t* __restrict__ W,
+                                                                                   f16_t* Y,
+                                                                                   float* __restrict__ mom_part, int M, int N,
+                                                                                   int K, int tiles_m, int groups_n,
+                                                                                   const f16_t* A, AddendGeo ag) {
+  conv1x1_kstream256_body<f16_t, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
 }
 
 struct KsPlan {
@@ -516,44 +538,56 @@ KsPlan ks_plan(int M, int K, int N) {
 }
 
 template <int WN, int PB, bool MOM, bool ADD>
-int ks_launch_m(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
-                const void* a, const AddendGeo& ag) {
+int ks_launch_m(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
+                hipStream_t st, const void* a, const AddendGeo& ag) {
   typedef KsGeo<WN, PB> G;
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_kstream_kernel<WN, PB, MOM, ADD>), dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
-                     G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n,
-                     (const bf16_t*)a, ag);
+  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_f16_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream_f16_kernel<WN, PB, MOM, ADD>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
+                       (f16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const f16_t*)a, ag);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream_kernel<WN, PB, MOM, ADD>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const bf16_t*)a, ag);
+  }
   return hip_status(hipGetLastError());
 }
 // a != null: the addend form (never with records)
 template <int WN, int PB>
-int ks_launch(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
-              const void* a, const AddendGeo& ag) {
-  if (a) return ks_launch_m<WN, PB, false, true>(p, x, w, y, nullptr, M, K, N, st, a, ag);
-  return part ? ks_launch_m<WN, PB, true, false>(p, x, w, y, part, M, K, N, st, a, ag)
-              : ks_launch_m<WN, PB, false, false>(p, x, w, y, part, M, K, N, st, a, ag);
+int ks_launch(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
+              hipStream_t st, const void* a, const AddendGeo& ag) {
+  if (a) return ks_launch_m<WN, PB, false, true>(p, x, w, y, nullptr, M, K, N, dtype, st, a, ag);
+  return part ? ks_launch_m<WN, PB, true, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag)
+              : ks_launch_m<WN, PB, false, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
 }
 template <bool MOM, bool ADD>
-int ks_launch256(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st,
-                 const void* a, const AddendGeo& ag) {
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_kstream256_kernel<MOM, ADD>), dim3((p.tiles_m * p.groups_n + 7) / 8 * 8), dim3(kKsWaves * kWave),
-                     Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n,
-                     (const bf16_t*)a, ag);
+int ks_launch256(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
+                 hipStream_t st, const void* a, const AddendGeo& ag) {
+  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_f16_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream256_f16_kernel<MOM, ADD>), grid, block, Ks256::kLds, st, (const f16_t*)x, (const f16_t*)w,
+                       (f16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const f16_t*)a, ag);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream256_kernel<MOM, ADD>), grid, block, Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const bf16_t*)a, ag);
+  }
   return hip_status(hipGetLastError());
 }
 
-int ks_dispatch(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st, const void* a,
-                const AddendGeo& ag) {
+int ks_dispatch(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st,
+                const void* a, const AddendGeo& ag) {
   const KsPlan p = ks_plan(M, K, N);
-  if (!p.wn) return MRLA_EUNSUPPORTED;
+  if (!p.wn || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
   if (p.big) {
-    if (a) return ks_launch256<false, true>(p, x, w, y, nullptr, M, K, N, st, a, ag);
-    return part ? ks_launch256<true, false>(p, x, w, y, part, M, K, N, st, a, ag)
-                : ks_launch256<false, false>(p, x, w, y, part, M, K, N, st, a, ag);
+    if (a) return ks_launch256<false, true>(p, x, w, y, nullptr, M, K, N, dtype, st, a, ag);
+    return part ? ks_launch256<true, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag)
+                : ks_launch256<false, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
   }
-  if (p.wn == 4) return p.pb == 2 ? ks_launch<4, 2>(p, x, w, y, part, M, K, N, st, a, ag) : ks_launch<4, 1>(p, x, w, y, part, M, K, N, st, a, ag);
-  return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, st, a, ag) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, st, a, ag);
+  if (p.wn == 4) return p.pb == 2 ? ks_launch<4, 2>(p, x, w, y, part, M, K, N, dtype, st, a, ag) : ks_launch<4, 1>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
+  return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, dtype, st, a, ag) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
 }
 
 }  // namespace
@@ -563,14 +597,14 @@ int conv1x1_kstream_rows(int M, int K, int N) { return ks_plan(M, K, N).tiles_m;
 int conv1x1_kstream_stages(int M, int K, int N) { return ks_plan(M, K, N).big ? Ks256::ST : kKsStages; }
 
 // part != null: moment records [conv1x1_kstream_rows()][N][MRLA_GEMM_MOMENTS] of the rounded outputs (one row per pixel tile)
-int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st) {
-  return ks_dispatch(x, w, y, part, M, K, N, st, nullptr, AddendGeo());
+int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st) {
+  return ks_dispatch(x, w, y, part, M, K, N, dtype, st, nullptr, AddendGeo());
 }
 
-// y = bf16(bf16(x w^T) + addend); addend: [M, N], or with sh * sw > 1 the compact [b, ceil(h/sh), ceil(w/sw), N] (M = b*h*w)
+// y = T(T(x w^T) + addend) in the element type T; addend: [M, N], or with sh * sw > 1 the compact [b, ceil(h/sh), ceil(w/sw), N] (M = b*h*w)
 int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
-                                  int wd, int sh, int sw, hipStream_t st) {
-  return ks_dispatch(x, w, y, nullptr, M, K, N, st, addend, make_addend_geo(b, h, wd, sh, sw));
+                                  int wd, int sh, int sw, int dtype, hipStream_t st) {
+  return ks_dispatch(x, w, y, nullptr, M, K, N, dtype, st, addend, make_addend_geo(b, h, wd, sh, sw));
 }
 
 }  // namespace mrla

@@ -1,4 +1,4 @@
-// Weight gradient of a 1x1 stride-1 convolution of channels_last bf16 activations as a split-M MFMA GEMM:
+// Weight gradient of a 1x1 stride-1 convolution of channels_last bf16 or fp16 activations as a split-M MFMA GEMM:
 //   dW[n, k] = sum_m dY[m, n] * X[m, k]        (M = b*h*w pixels; dY [M, N] and X [M, K] both channel-contiguous)
 // Reference: the backward of the bottleneck's conv1 / conv3 (resnet/models/resnet_mrla_light.py:93,100, nn.Conv2d 1x1).
 //
@@ -23,16 +23,15 @@
 //     stages (measured: 1 us per chunk whatever the depth).
 #include <algorithm>
 
+#include "conv1x1_elem.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
 namespace mrla {
 namespace {
 
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 wg_bf16x4 __attribute__((ext_vector_type(4)));
 typedef short wg_s16x4 __attribute__((ext_vector_type(4)));
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
+typedef c1_f32x16 wg_f32x16;
 typedef __attribute__((address_space(3))) wg_s16x4* lds_s16x4_ptr;
 
 constexpr int kPC = 32;                 // pixels per stage
@@ -89,19 +88,19 @@ __device__ __forceinline__ void frag_fence(Frag& f, bool wait) {
   if (wait) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f.lo), "+v"(f.hi) : "n"(N) : "memory");
   else asm volatile("" : "+v"(f.lo), "+v"(f.hi)::"memory");      // rides on the wait of the fragment fenced just before
 }
-__device__ __forceinline__ wg_bf16x8 frag_value(const Frag& f) {
-  return __builtin_bit_cast(wg_bf16x8, __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7));
+template <typename T>
+__device__ __forceinline__ typename Elem16<T>::x8 frag_value(const Frag& f) {
+  return __builtin_bit_cast(typename Elem16<T>::x8, __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 __device__ __forceinline__ unsigned wg_lds_addr(const void* p) {
   return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
 }
 
 // grid: tiles * splits workgroups (tiles = (N/TN)*(K/TK)) padded to a multiple of 8; 256 threads; LDS = ST * SB
-template <int TN, int TK, int ST, int PC>
-__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf16_t* __restrict__ dY,
-                                                                        const bf16_t* __restrict__ X,
-                                                                        float* __restrict__ part, int M, int N, int K,
-                                                                        int chunks_per_wg, int nsplits) {
+template <typename T, int TN, int TK, int ST, int PC>
+__device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, const T* __restrict__ X,
+                                                   float* __restrict__ part, int M, int N, int K, int chunks_per_wg,
+                                                   int nsplits) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef WgGeo<TN, TK, PC> G;
   constexpr int CPRY = TN / 8, CPRX = TK / 8;            // 16-byte chunks per tile row
@@ -123,8 +122,8 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf
   const int nch = min(chunks_per_wg, chunks_total - c_begin);      // >= 1 by construction of the grid
 
   // ---- DMA plan: wave-instruction u of a stage moves 1 KB = 64/CPR tile rows; this wave issues u = wave + 4*i ----
-  const auto rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(dY), 0, (int)((size_t)M * N * 2), MRLA_WG_FLAGS);
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)((size_t)M * K * 2), MRLA_WG_FLAGS);
+  const auto rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(dY), 0, (int)((size_t)M * N * 2), MRLA_WG_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_WG_FLAGS);
   unsigned voffY[G::NIY], voffX[G::NIX];
 #pragma unroll
   for (int i = 0; i < G::NIY; ++i) {
@@ -190,7 +189,7 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf
     for (int i = 0; i < G::BN; ++i)
 #pragma unroll
       for (int j = 0; j < G::BK; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_value(fa[buf][i]), frag_value(fb[buf][j]), acc[i][j], 0, 0, 0);
+        Elem16<T>::mfma(acc[i][j], frag_value<T>(fa[buf][i]), frag_value<T>(fb[buf][j]));
   };
 #pragma unroll
   for (int j = 0; j < ST - 1; ++j) issue(j);
@@ -241,11 +240,27 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf
 #endif
 }
 
+template <int TN, int TK, int ST, int PC>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf16_t* __restrict__ dY,
+                                                                        const bf16_t* __restrict__ X,
+                                                                        float* __restrict__ part, int M, int N, int K,
+                                                                        int chunks_per_wg, int nsplits) {
+  conv1x1_wgrad_body<bf16_t, TN, TK, ST, PC>(dY, X, part, M, N, K, chunks_per_wg, nsplits);
+}
+// the fp16 instances (a name of their own: see conv1x1_fwd_f16_kernel in conv1x1.hip)
+template <int TN, int TK, int ST, int PC>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_f16_kernel(const f16_t* __restrict__ dY,
+                                                                            const f16_t* __restrict__ X,
+                                                                            float* __restrict__ part, int M, int N, int K,
+                                                                            int chunks_per_wg, int nsplits) {
+  conv1x1_wgrad_body<f16_t, TN, TK, ST, PC>(dY, X, part, M, N, K, chunks_per_wg, nsplits);
+}
+
 // dW[e] = sum over splits of part[s][e] in a fixed order: a workgroup takes 64 outputs, its 16 groups of 16 lanes take
 // every 16th split with 16-byte loads, LDS folds the groups
 template <typename TO>
-__global__ __launch_bounds__(256) void conv1x1_wgrad_reduce_kernel(const float* __restrict__ part, TO* __restrict__ dW,
-                                                                   int splits, int NK) {
+__device__ __forceinline__ void conv1x1_wgrad_reduce_body(const float* __restrict__ part, TO* __restrict__ dW, int splits,
+                                                          int NK) {
   __shared__ float4 red[16][16];
   const int q = threadIdx.x & 15, g = threadIdx.x >> 4;
   const int e = blockIdx.x * 64 + q * 4;                 // NK % 64 == 0
@@ -271,6 +286,15 @@ __global__ __launch_bounds__(256) void conv1x1_wgrad_reduce_kernel(const float* 
     for (int i = 0; i < 16; ++i) t += reinterpret_cast<const float*>(&red[i][qq])[cc];
     dW[blockIdx.x * 64 + threadIdx.x] = from_f<TO>(t);
   }
+}
+template <typename TO>
+__global__ __launch_bounds__(256) void conv1x1_wgrad_reduce_kernel(const float* __restrict__ part, TO* __restrict__ dW,
+                                                                   int splits, int NK) {
+  conv1x1_wgrad_reduce_body<TO>(part, dW, splits, NK);
+}
+__global__ __launch_bounds__(256) void conv1x1_wgrad_reduce_f16_kernel(const float* __restrict__ part, f16_t* __restrict__ dW,
+                                                                       int splits, int NK) {
+  conv1x1_wgrad_reduce_body<f16_t>(part, dW, splits, NK);
 }
 
 struct WgPlan {
@@ -299,12 +323,19 @@ WgPlan wgrad_plan(int M, int K, int N) {
 }
 
 template <int TN, int TK, int ST, int PC>
-int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int M, int K, int N, hipStream_t st) {
+int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st) {
   typedef WgGeo<TN, TK, PC> G;
   const size_t lds = (size_t)ST * G::SB;
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_wgrad_kernel<TN, TK, ST, PC>), dim3((p.tiles * p.splits + 7) / 8 * 8), dim3(kWgWaves * kWave), lds, st,
-                     (const bf16_t*)dy, (const bf16_t*)x, part, M, N, K, p.chunks_per_wg, p.splits);
+  const dim3 grid((p.tiles * p.splits + 7) / 8 * 8), block(kWgWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const f16_t*)dy, (const f16_t*)x, part,
+                       M, N, K, p.chunks_per_wg, p.splits);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wgrad_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const bf16_t*)dy, (const bf16_t*)x, part,
+                       M, N, K, p.chunks_per_wg, p.splits);
+  }
   return MRLA_OK;
 }
 
@@ -323,13 +354,13 @@ int conv1x1_wgrad_plan(int M, int K, int N, int* out) {
   return MRLA_OK;
 }
 
-int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N,
+int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
                          hipStream_t st) {
   const WgPlan p = wgrad_plan(M, K, N);
-  if (!p.tiles) return MRLA_EUNSUPPORTED;
+  if (!p.tiles || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
   int rc = MRLA_EUNSUPPORTED;
 #define MRLA_WG_TILE(A, B) \
-  if (p.tn == A && p.tk == B) rc = launch_tile<A, B, kWgStages, kPC>(p, dy, x, part, M, K, N, st);
+  if (p.tn == A && p.tk == B) rc = launch_tile<A, B, kWgStages, kPC>(p, dy, x, part, M, K, N, dtype, st);
   MRLA_WG_TILE(64, 64) MRLA_WG_TILE(64, 128) MRLA_WG_TILE(64, 256) MRLA_WG_TILE(128, 64) MRLA_WG_TILE(128, 128)
   MRLA_WG_TILE(128, 256) MRLA_WG_TILE(256, 64) MRLA_WG_TILE(256, 128)
 #undef MRLA_WG_TILE
@@ -337,6 +368,8 @@ int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, i
   const int NK = N * K;
   if (dw_f32)      // the fp32 master weight's gradient directly (no cast kernel behind an autocast convolution)
     hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<float>, dim3(NK / 64), dim3(256), 0, st, part, (float*)dw, p.splits, NK);
+  else if (dtype == MRLA_F16)
+    hipLaunchKernelGGL(conv1x1_wgrad_reduce_f16_kernel, dim3(NK / 64), dim3(256), 0, st, part, (f16_t*)dw, p.splits, NK);
   else
     hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<bf16_t>, dim3(NK / 64), dim3(256), 0, st, part, (bf16_t*)dw, p.splits, NK);
   return hip_status(hipGetLastError());

@@ -1,5 +1,5 @@
 // 1x1 stride-1 convolution with a wide output (N % 256 == 0) as a streaming MFMA GEMM, BatchNorm-statistics epilogue:
-//   Y[M, N] = X[M, K] * W[N, K]^T (+ A[M, N])      K in {64, 128, 256}; bf16 in/out, fp32 accumulate
+//   Y[M, N] = X[M, K] * W[N, K]^T (+ A[M, N])      K in {64, 128, 256}; bf16 or fp16 in/out, fp32 accumulate
 //   part[row, n, 0..3] = per-workgroup moment record of the bf16-ROUNDED outputs of channel n (MRLA_GEMM_MOMENTS):
 //                        sum (y - p), sum (y - p)^2, the pivot p (the workgroup's first output of the channel), pixel count
 // Reference: the bottleneck's conv3 / bn3 (resnet/models/resnet_mrla_light.py:100-101) and, with the operands swapped
@@ -31,8 +31,7 @@
 namespace mrla {
 namespace {
 
-typedef __bf16 cw_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float cw_f32x16 __attribute__((ext_vector_type(16)));
+typedef c1_f32x16 cw_f32x16;
 
 #define MRLA_CW_FLAGS 0x00020000          /* raw buffer descriptor word 3 (as nhwc_rows.h) */
 constexpr int kCwWaves = 8;
@@ -74,15 +73,14 @@ template <int CPR>
 __device__ __forceinline__ int cw_swz(int row) { return CPR >= 16 ? (row & 15) : ((row >> 1) & 7); }
 __device__ __forceinline__ int cw_oswz(int row) { return row & 7; }
 
-template <int KS, bool MOM, bool ADD, bool SP>
-__global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf16_t* __restrict__ X,
-                                                                       const bf16_t* __restrict__ W,
-                                                                       const bf16_t* __restrict__ A, bf16_t* __restrict__ Y,
-                                                                       float* __restrict__ part, int M, int N,
-                                                                       int units_per_wg, int nsplits, int rows_total,
-                                                                       AddendGeo ag) {
+template <typename T, int KS, bool MOM, bool ADD, bool SP>
+__device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const T* __restrict__ W, const T* __restrict__ A,
+                                                  T* __restrict__ Y, float* __restrict__ part, int M, int N,
+                                                  int units_per_wg, int nsplits, int rows_total, AddendGeo ag) {
   static_assert(ADD || !SP, "a compact addend is an addend");
 #if defined(__HIP_DEVICE_COMPILE__)
+  typedef Elem16<T> E;
+  typedef typename E::x8 cw_x8;
   typedef CwGeo<KS, ADD> G;
   constexpr int K = G::K, CPR = K / 8, UST = G::UST;
   extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -101,16 +99,16 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
   const int n0 = cg * kCwTN + wave * 32;
 
   // ---- this wave's 32 rows of W, for the whole kernel ----
-  cw_bf16x8 wf[KS];
+  cw_x8 wf[KS];
   {
     const u32x4* wp = reinterpret_cast<const u32x4*>(W + (size_t)(n0 + r) * K + h * 8);
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) wf[ks] = __builtin_bit_cast(cw_bf16x8, wp[ks * 2]);
+    for (int ks = 0; ks < KS; ++ks) wf[ks] = __builtin_bit_cast(cw_x8, wp[ks * 2]);
   }
 
   // ---- DMA plan ----
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(X), 0, (int)((size_t)M * K * 2), MRLA_CW_FLAGS);
-  const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(ADD ? A : X), 0,
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_CW_FLAGS);
+  const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(ADD ? A : X), 0,
                                                      ADD ? (int)((size_t)(SP ? ag.rows : M) * N * 2) : 0, MRLA_CW_FLAGS);
   unsigned voffX[G::NIX], voffA[ADD ? G::NIA : 1];
   constexpr bool kIdleWaves = G::XB / 1024 < kCwWaves;          // K = 64: four real X instructions, waves 4-7 issue a dummy
@@ -171,7 +169,7 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
   const int srow = threadIdx.x >> 5, schunk = threadIdx.x & 31;
   const unsigned sld0 = lds0 + G::kXRing + srow * (kCwTN * 2) + ((schunk ^ cw_oswz(srow)) << 4);
   const unsigned sld1 = sld0 + 16 * (kCwTN * 2);                             // (row + 16: same swizzle, (row+16)&7 == row&7)
-  bf16_t* yrow = Y + ((size_t)u_begin * 32 + srow) * N + cg * kCwTN + schunk * 8;
+  T* yrow = Y + ((size_t)u_begin * 32 + srow) * N + cg * kCwTN + schunk * 8;
 
   // BatchNorm moments of the rounded outputs, per lane (register = channel, lane = pixel), taken about a pivot: the
   // workgroup's first output of the channel (lane r = 0 of the half-wave in the first unit).  The one-pass variance
@@ -218,9 +216,9 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
       }
 #pragma unroll
       for (int ks = 0; ks < KC; ++ks)
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kc * KC + ks], __builtin_bit_cast(cw_bf16x8, xf[cur][ks]), acc, 0, 0, 0);
+        E::mfma(acc, wf[kc * KC + ks], __builtin_bit_cast(cw_x8, xf[cur][ks]));
     }
-    // lane = pixel r; register e = channel 8*(e/4) + 4*h + e%4 of the wave's 32.  Round pairs of neighbours to bf16.
+    // lane = pixel r; register e = channel 8*(e/4) + 4*h + e%4 of the wave's 32.  Round pairs of neighbours to the element type.
     // (in piece order after the exchange below: piece g = channels 16g + 8h .. 16g + 8h + 7, 16 bytes of the pixel's row)
     unsigned p[8];
     float av[16];
@@ -245,43 +243,35 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
       const unsigned aw[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        av[2 * i] += __uint_as_float(aw[i] << 16);
-        av[2 * i + 1] += __uint_as_float(aw[i] & 0xffff0000u);
+        av[2 * i] += E::lo(aw[i]);
+        av[2 * i + 1] += E::hi(aw[i]);
       }
     }
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
-      bf16x2 pr;
-      pr[0] = from_f<bf16_t>(av[2 * i]);
-      pr[1] = from_f<bf16_t>(av[2 * i + 1]);
-      p[i] = __builtin_bit_cast(unsigned, pr);
-    }
+    for (int i = 0; i < 8; ++i) p[i] = E::pack(av[2 * i], av[2 * i + 1]);
     if (MOM) {
-      float val[16];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        val[2 * i] = __uint_as_float(p[i] << 16);
-        val[2 * i + 1] = __uint_as_float(p[i] & 0xffff0000u);
-      }
+      // (pair by pair: the sixteen decoded values need not be live together)
       if (u == 0) {              // (uniform) the pivots: this half-wave's pixel 0, which always exists
 #pragma unroll
-        for (int i = 0; i < 16; ++i) pv[i] = __shfl(val[i], h * 32, kWave);
+        for (int i = 0; i < 8; ++i) {
+          pv[2 * i] = __shfl(E::lo(p[i]), h * 32, kWave);
+          pv[2 * i + 1] = __shfl(E::hi(p[i]), h * 32, kWave);
+        }
       }
       if (!(ragged_tail && u == nun - 1)) {
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float dlt = val[i] - pv[i];
-          s1[i] += dlt;
-          s2[i] = fmaf(dlt, dlt, s2[i]);
+        for (int i = 0; i < 8; ++i) {
+          const float dl = E::lo(p[i]) - pv[2 * i], dh = E::hi(p[i]) - pv[2 * i + 1];
+          s1[2 * i] += dl;     s2[2 * i] = fmaf(dl, dl, s2[2 * i]);
+          s1[2 * i + 1] += dh; s2[2 * i + 1] = fmaf(dh, dh, s2[2 * i + 1]);
         }
       } else {                   // (uniform) the one unit with pixels past the end: those do not count
         const bool live = (u_begin + u) * 32 + r < M;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const float dlt = live ? val[i] - pv[i] : 0.f;
-          s1[i] += dlt;
-          s2[i] = fmaf(dlt, dlt, s2[i]);
+        for (int i = 0; i < 8; ++i) {
+          const float dl = live ? E::lo(p[i]) - pv[2 * i] : 0.f, dh = live ? E::hi(p[i]) - pv[2 * i + 1] : 0.f;
+          s1[2 * i] += dl;     s2[2 * i] = fmaf(dl, dl, s2[2 * i]);
+          s1[2 * i + 1] += dh; s2[2 * i + 1] = fmaf(dh, dh, s2[2 * i + 1]);
         }
       }
     }
@@ -316,7 +306,7 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
       cw_fence<0>(v0, true);
       cw_fence<0>(v1, false);
       const int pix = (u_begin + u) * 32 + srow;
-      bf16_t* yp = yrow + (size_t)u * 32 * N;
+      T* yp = yrow + (size_t)u * 32 * N;
       if (pix < M) *reinterpret_cast<u32x4*>(yp) = v0;
       if (pix + 16 < M) *reinterpret_cast<u32x4*>(yp + (size_t)16 * N) = v1;
     }
@@ -353,6 +343,26 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf1
 #endif
 }
 
+template <int KS, bool MOM, bool ADD, bool SP>
+__global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_kernel(const bf16_t* __restrict__ X,
+                                                                       const bf16_t* __restrict__ W,
+                                                                       const bf16_t* __restrict__ A, bf16_t* __restrict__ Y,
+                                                                       float* __restrict__ part, int M, int N,
+                                                                       int units_per_wg, int nsplits, int rows_total,
+                                                                       AddendGeo ag) {
+  conv1x1_wide_body<bf16_t, KS, MOM, ADD, SP>(X, W, A, Y, part, M, N, units_per_wg, nsplits, rows_total, ag);
+}
+// the fp16 instances (a name of their own: see conv1x1_fwd_f16_kernel)
+template <int KS, bool MOM, bool ADD, bool SP>
+__global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_f16_kernel(const f16_t* __restrict__ X,
+                                                                           const f16_t* __restrict__ W,
+                                                                           const f16_t* __restrict__ A, f16_t* __restrict__ Y,
+                                                                           float* __restrict__ part, int M, int N,
+                                                                           int units_per_wg, int nsplits, int rows_total,
+                                                                           AddendGeo ag) {
+  conv1x1_wide_body<f16_t, KS, MOM, ADD, SP>(X, W, A, Y, part, M, N, units_per_wg, nsplits, rows_total, ag);
+}
+
 struct CwPlan {
   int groups = 0, splits = 0, units_per_wg = 0, rows = 0;
 };
@@ -373,14 +383,22 @@ CwPlan cw_plan(int M, int K, int N) {
 }
 
 template <int KS, bool MOM, bool ADD, bool SP = false>
-int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void* y, float* part, int M, int N, hipStream_t st,
-              const AddendGeo& ag = AddendGeo()) {
+int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void* y, float* part, int M, int N, int dtype,
+              hipStream_t st, const AddendGeo& ag = AddendGeo()) {
   typedef CwGeo<KS, ADD> G;
   static_assert(G::kLds <= 160 * 1024, "LDS");
-  if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD, SP>), dim3((p.groups * p.splits + 7) / 8 * 8), dim3(kCwWaves * kWave),
-                     G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)a, (bf16_t*)y, part, M, N,
-                     p.units_per_wg, p.splits, p.rows, ag);
+  const dim3 grid((p.groups * p.splits + 7) / 8 * 8), block(kCwWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_f16_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wide_f16_kernel<KS, MOM, ADD, SP>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
+                       (const f16_t*)a, (f16_t*)y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
+  } else if (dtype == MRLA_BF16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD, SP>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       (const bf16_t*)a, (bf16_t*)y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
+  } else {
+    return MRLA_EUNSUPPORTED;
+  }
   return hip_status(hipGetLastError());
 }
 
@@ -405,15 +423,15 @@ int conv1x1_wide_plan(int M, int K, int N, int add, int* out) {
 }
 
 int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* y, float* part, int M, int K, int N,
-                        hipStream_t st) {
+                        int dtype, hipStream_t st) {
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
 #define MRLA_CW_CALL(KS)                                                                         \
   {                                                                                              \
-    if (addend) return part ? cw_launch<KS, true, true>(p, x, w, addend, y, part, M, N, st)      \
-                            : cw_launch<KS, false, true>(p, x, w, addend, y, part, M, N, st);    \
-    return part ? cw_launch<KS, true, false>(p, x, w, addend, y, part, M, N, st)                 \
-                : cw_launch<KS, false, false>(p, x, w, addend, y, part, M, N, st);               \
+    if (addend) return part ? cw_launch<KS, true, true>(p, x, w, addend, y, part, M, N, dtype, st)      \
+                            : cw_launch<KS, false, true>(p, x, w, addend, y, part, M, N, dtype, st);    \
+    return part ? cw_launch<KS, true, false>(p, x, w, addend, y, part, M, N, dtype, st)                 \
+                : cw_launch<KS, false, false>(p, x, w, addend, y, part, M, N, dtype, st);               \
   }
   switch (K) {
     case 64: MRLA_CW_CALL(4)
@@ -426,14 +444,14 @@ int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* 
 
 // y = x w^T + the compact addend [b, ceil(h/sh), ceil(w/sw), N] of a strided subsample (see conv1x1_addend.h); M = b*h*w
 int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
-                               int wd, int sh, int sw, hipStream_t st) {
+                               int wd, int sh, int sw, int dtype, hipStream_t st) {
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
   const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
   switch (K) {
-    case 64: return cw_launch<4, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
-    case 128: return cw_launch<8, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
-    case 256: return cw_launch<16, false, true, true>(p, x, w, addend, y, nullptr, M, N, st, ag);
+    case 64: return cw_launch<4, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
+    case 128: return cw_launch<8, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
+    case 256: return cw_launch<16, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
     default: return MRLA_EUNSUPPORTED;
   }
 }

@@ -169,14 +169,14 @@ int launch_affine_act(const void* x, const void* dy, const float* a, const float
 
 // light_nhwc.hip / bnact_nhwc.hip -- channels_last variants
 int nhwc_images_per_group(int B, int C, int W);
-// conv1x1.hip -- 1x1 convolution as an MFMA GEMM with a BatchNorm-moments epilogue (bf16)
+// conv1x1.hip -- 1x1 convolution as an MFMA GEMM with a BatchNorm-moments epilogue (dtype: MRLA_BF16 or MRLA_F16)
 int conv1x1_rows(int M, int K, int N);
 int conv1x1_plan(int M, int K, int N, int add, int* out);
-int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st);
+int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st);
 // ... + addend (the shortcut's gradient in the input-gradient use): [M, N], or compact [b, ceil(h/sh), ceil(w/sw), N]
 int conv1x1_addend_supported(int M, int K, int N);
 int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h, int wd,
-                          int sh, int sw, hipStream_t st);
+                          int sh, int sw, int dtype, hipStream_t st);
 // stem_pool_nhwc.hip -- maxpool3x3/s2/p1(relu(bn(x))) without the intermediate tensor (channels_last, C % 64 == 0)
 int bn_pool_rows(int B, int C, int H, int W);
 int launch_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int B, int C, int H, int W,
@@ -189,23 +189,23 @@ int launch_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, cons
 int conv1x1_wide_rows(int M, int K, int N);
 int conv1x1_wide_plan(int M, int K, int N, int add, int* out);
 int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* y, float* part, int M, int K, int N,
-                        hipStream_t st);
+                        int dtype, hipStream_t st);
 int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
-                               int wd, int sh, int sw, hipStream_t st);      // compact addend of a strided subsample
+                               int wd, int sh, int sw, int dtype, hipStream_t st);      // compact addend of a strided subsample
 // conv1x1_kstream.hip -- the same product for wide reductions (K >= 512): both operands streamed through LDS; the tile copy-out takes the BatchNorm moment records as well
 int conv1x1_kstream_supported(int M, int K, int N);
 int conv1x1_kstream_stages(int M, int K, int N);      // LDS stages of the kernel the planner picks (3, or 4: the 256 x 256 tile)
 int conv1x1_kstream_rows(int M, int K, int N);        // rows of the moment records (one per pixel tile)
-int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, hipStream_t st);
+int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st);
 int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
-                                  int wd, int sh, int sw, hipStream_t st);
-// conv1x1_wgrad.hip -- its weight gradient dW[n,k] = sum_m dY[m,n] X[m,k] as a split-M MFMA GEMM (bf16)
+                                  int wd, int sh, int sw, int dtype, hipStream_t st);
+// conv1x1_wgrad.hip -- its weight gradient dW[n,k] = sum_m dY[m,n] X[m,k] as a split-M MFMA GEMM (bf16 or fp16)
 int conv1x1_wgrad_rows(int M, int K, int N);
 int conv1x1_wgrad_plan(int M, int K, int N, int* out);
-int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N,
+int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
                          hipStream_t st);
-// weight_bank.hip -- all eligible fp32 conv weights -> bf16 copies (+ transposes) in one launch
-int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, hipStream_t st);
+// weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
+int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)
 int launch_light_stats_fwd_wide(const void* x, const void* o, const float* wv, float* mom, void* xout, const float* psc,
                                 const float* psh, void* vout, int B, int C, int H, int W, int dtype, int act,

@@ -125,7 +125,7 @@ def current_bookkeeping():
 def batched_bookkeeping(n_drop_paths=0, bank=None):
     """Inside: train-mode BatchNorm counters handled by bn_act / the fused tails are collected and bumped with ONE
     torch._foreach_add_ on exit, layers.drop_path_scale serves stochastic-depth rows from one table, and conv_bn_act
-    takes the bf16 working copies of its weights from `bank` (a refreshed WeightBank)."""
+    takes the 16-bit working copies of its weights from `bank` (a refreshed WeightBank)."""
     prev, book = current_bookkeeping(), _Bookkeeping(n_drop_paths, bank)
     _TLS.book = book
     try:
@@ -1332,8 +1332,8 @@ def bn_relu_maxpool(x, bn, pool):
 # 1x1 stride-1 convolution as an MFMA GEMM with the BatchNorm statistics in its epilogue
 # ======================================================================================================
 class WeightBank:
-    """bf16 working copies [n, k] (and transposes [k, n]) of a model's fp32 1x1-convolution weights, refreshed by ONE
-    launch of mrla_weight_bank_refresh per training step: what torch.autocast does with one cast kernel per convolution
+    """16-bit working copies [n, k] (and transposes [k, n]) of a model's fp32 1x1-convolution weights, refreshed by ONE
+    launch of mrla_weight_bank_refresh_dt per training step: what torch.autocast does with one cast kernel per convolution
     and forward, and what the input-gradient GEMM needed one transposing copy per call for.  Built lazily for the
     eligible convolutions of a model (1x1, stride 1, no bias, fp32 weight, both channel counts multiples of 64);
     `refresh()` re-launches whenever gradients are enabled (a training forward: the optimizer will have moved the masters,
@@ -1341,11 +1341,16 @@ class WeightBank:
     replays of that graph update the masters without touching any Python-side version counter, so after them the
     counters prove nothing.  Only a grad-free forward outside any capture history (validation loops) skips the launch
     while every weight's version counter stands still; writes the counters cannot see (`p.data.copy_(...)`) need
-    `invalidate()`."""
+    `invalidate()`.
+    The copies are of ONE dtype at a time, the one the bank was last refreshed for: bf16 unless refresh() is told otherwise
+    or runs under fp16 CUDA autocast.  A change of dtype rebuilds the copies and the table like a first use (not
+    capturable); get() hands copies out only to a caller that asks for the dtype they are of, so a bf16 bank never
+    reaches an fp16 GEMM."""
 
     def __init__(self, convs):
         self.convs = [c for c in convs if self.eligible(c)]
         self.key = self.sig = None
+        self.dtype = torch.bfloat16
         self.captured = False          # sticky: a refresh is part of some HIP graph
         self.entries = {}
 
@@ -1361,10 +1366,11 @@ class WeightBank:
                 and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
                 and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
 
-    def _build(self, live):
+    def _build(self, live, dtype):
         dev = live[0].weight.device
         total = sum(c.weight.numel() for c in live)
-        self.flat = torch.empty((2, total), dtype=torch.bfloat16, device=dev)
+        self.dtype = dtype
+        self.flat = torch.empty((2, total), dtype=dtype, device=dev)
         rows, off, self.entries, self.max_tiles = [], 0, {}, 1
         for c in live:
             n, k = c.out_channels, c.in_channels
@@ -1376,35 +1382,44 @@ class WeightBank:
         self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
         self.n = len(rows)
 
-    def refresh(self):
+    def refresh(self, dtype=None):
+        """dtype: torch.bfloat16 or torch.float16; None: the CUDA autocast dtype when autocast is on and is one of the two,
+        else bf16."""
+        if dtype is None:
+            dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else torch.bfloat16
+            if dtype not in (torch.bfloat16, torch.float16):
+                dtype = torch.bfloat16
+        elif dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"WeightBank.refresh: dtype must be torch.bfloat16 or torch.float16, got {dtype}")
         live = [c for c in self.convs if c.weight.is_cuda and c.weight.dtype == torch.float32
                 and (c.weight.is_contiguous() or c.weight.is_contiguous(memory_format=_CL))]
         if not live:
             self.entries = {}
             return self
-        sig = tuple((id(c), c.weight.data_ptr()) for c in live)
+        sig = (dtype,) + tuple((id(c), c.weight.data_ptr()) for c in live)
         capturing = torch.cuda.is_current_stream_capturing()
-        if sig != self.sig:                       # first use, or the parameters moved (.to(), load with assign=...)
+        if sig != self.sig:        # first use, the parameters moved (.to(), load with assign=...), or another dtype is asked for
             if capturing:                         # (the table is built with a host-to-device copy: not capturable)
-                raise L.MrlaHipError("WeightBank: first use (or moved parameters) inside a HIP graph capture; run one "
-                                     "forward of the model eagerly before capturing it")
-            self._build(live)
+                raise L.MrlaHipError("WeightBank: first use (or moved parameters, or a change of dtype) inside a HIP graph "
+                                     "capture; run one forward of the model eagerly before capturing it (in the precision of the capture)")
+            self._build(live, dtype)
             self.sig, self.key = sig, None
         key = tuple(c.weight._version for c in live)
         self.captured = self.captured or capturing
         if key != self.key or self.captured or torch.is_grad_enabled():
             with torch.cuda.device(self.table.device):
-                L.call("mrla_weight_bank_refresh", _ptr(self.table), self.n, self.max_tiles, _stream())
+                L.call("mrla_weight_bank_refresh_dt", _ptr(self.table), self.n, self.max_tiles, _DT[self.dtype], _stream())
             self.key = key
         return self
 
-    def get(self, conv):
-        """(w bf16 [n, k], w^T bf16 [k, n]) of `conv`, or None when it is not in the bank."""
-        return self.entries.get(id(conv))
+    def get(self, conv, dtype=torch.bfloat16):
+        """(w [n, k], w^T [k, n]) of `conv` in `dtype`, or None when it is not in the bank or the bank's copies are of
+        another dtype."""
+        return self.entries.get(id(conv)) if dtype == self.dtype else None
 
 
 class _Conv1x1Fn(torch.autograd.Function):
-    """y = conv2d(x, w) for a bias-free 1x1 stride-1 convolution of a channels_last bf16 tensor, plus the partial
+    """y = conv2d(x, w) for a bias-free 1x1 stride-1 convolution of a channels_last bf16 or fp16 tensor, plus the partial
     moment-record rows of y the following BatchNorm needs (mrla_conv1x1_fwd: MRLA_GEMM_MOMENTS records, one row per
     workgroup pixel range -- the resident-weight kernels and the K-streaming kernel of the wide reductions, k >= 512, both
     write them; `mrla_bn_stats_fwd_rows` merges them).  Shapes the GEMMs do not take (mrla_conv1x1_rows < 0) run the stock
@@ -1414,7 +1429,7 @@ class _Conv1x1Fn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def forward(ctx, x, w, want_moments, passthrough=False, w16=None, w16t=None, sub=None):
-        """w16 / w16t: bf16 working copies [n, k] / [k, n] of an fp32 master weight `w` (WeightBank); the weight gradient
+        """w16 / w16t: working copies [n, k] / [k, n], of x's dtype, of an fp32 master weight `w` (WeightBank); the weight gradient
         is then returned in the master's dtype straight from the reduction kernel.
         sub = (sh, sw), with passthrough: the third output is x[:, :, ::sh, ::sw] (dense channels_last) instead of x -- the
         input of the block's strided downsample convolution.  Its gradient then comes back COMPACT, and the input-gradient
@@ -1556,14 +1571,17 @@ def _strided_1x1(conv):
 
 
 def conv1x1_applies(conv, x, strided=False):
-    """True when `conv(x)` belongs on the HIP GEMMs: nn.Conv2d 1x1 / stride 1 / no bias, channels_last bf16 input, and a
-    shape the forward kernel (mrla_conv1x1_rows) or the weight-gradient kernel (mrla_conv1x1_wgrad_rows) takes.
+    """True when `conv(x)` belongs on the HIP GEMMs: nn.Conv2d 1x1 / stride 1 / no bias, channels_last bf16 or fp16 input,
+    and a shape the forward kernel (mrla_conv1x1_rows) or the weight-gradient kernel (mrla_conv1x1_wgrad_rows) takes.
     strided: the question is asked for a strided 1x1 convolution, which runs as the stride-1 GEMM on the subsampled input
-    (`x` is the full-size input; the pixel count is the subsampled one)."""
+    (`x` is the full-size input; the pixel count is the subsampled one).  That question is answered for bf16 ONLY: a strided
+    fp16 downsample keeps its route -- one stock convolution on the subsampled input (conv_bn_act) -- although the kernels,
+    the compact addend of mrla_conv1x1_fwd_addend included, take fp16 at the C ABI; the models do not reach them yet."""
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1) and (strided or conv.stride == (1, 1))
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=_CL)
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in ((torch.bfloat16,) if strided else (torch.bfloat16, torch.float16))
+            and x.is_contiguous(memory_format=_CL)
             and x.data_ptr() % 16 == 0):               # (the kernels move 16-byte fragments)
         return False
     b, k, h, w = x.shape
@@ -1571,15 +1589,16 @@ def conv1x1_applies(conv, x, strided=False):
         return False
     if strided and strided != "pre":                       # ("pre": `x` is the subsampled input already)
         h, w = (h + conv.stride[0] - 1) // conv.stride[0], (w + conv.stride[1] - 1) // conv.stride[1]
-    lib, m, n = L.load(), b * h * w, conv.out_channels
-    if lib.mrla_conv1x1_rows(m, k, n, L.BF16) >= 0:
+    lib, m, n, dt = L.load(), b * h * w, conv.out_channels, _DT[x.dtype]
+    if lib.mrla_conv1x1_rows(m, k, n, dt) >= 0:
         return True
-    return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, L.BF16) > 0
+    return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, dt) > 0
 
 
 def shortcut_subsample(downsample, x):
     """(sh, sw) when `downsample` is the strided 1x1 convolution + BatchNorm of a stage's first block
-    (resnet_mrla_light.py:196-199) and runs on the GEMMs for the block input `x`, else None.  The block then asks conv1 for
+    (resnet_mrla_light.py:196-199) and runs on the GEMMs for the block input `x` (bf16 only: conv1x1_applies), else None.
+    The block then asks conv1 for
     the subsampled input (conv_bn_act(..., passthrough=True, subsample=...)) and hands it on with presampled=True."""
     if not (isinstance(downsample, torch.nn.Sequential) and len(downsample) == 2 and _strided_1x1(downsample[0])):
         return None
@@ -1616,9 +1635,9 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
         wt, w16, w16t = conv.weight, None, None
         if wt.dtype != x.dtype:
             book = current_bookkeeping()
-            held = book.bank.get(conv) if (book is not None and book.bank is not None and wt.dtype == torch.float32) else None
+            held = book.bank.get(conv, x.dtype) if (book is not None and book.bank is not None and wt.dtype == torch.float32) else None
             if held is not None:
-                w16, w16t = held                     # the step's bf16 working copy and its transpose (WeightBank)
+                w16, w16t = held                     # the step's working copy in x's dtype and its transpose (WeightBank)
             else:
                 wt = wt.to(x.dtype)                  # what autocast does for the stock convolution (differentiable)
         if passthrough and torch.is_grad_enabled() and x.requires_grad:

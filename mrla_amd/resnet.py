@@ -78,11 +78,12 @@ class _BottleneckTrunk(nn.Module):
         """Everything up to, but not including, the shortcut add + ReLU: (bn3 output, identity).
         defer_bn3 (bool, or a predicate on conv3's output): only bn3's statistics are taken here; its affine is applied
         by the consumer's first pass."""
-        # 1x1 convolutions: HIP MFMA GEMM with the BatchNorm statistics in its epilogue when eligible (bf16, channels_last).
+        # 1x1 convolutions: HIP MFMA GEMM with the BatchNorm statistics in its epilogue when eligible (bf16 or fp16, channels_last).
         # The block input's second consumer -- the shortcut itself, or the downsample branch -- takes it through conv1's
         # autograd node, so that its gradient is added in the epilogue of conv1's input-gradient GEMM instead of by
         # autograd's accumulation pass.  In front of a strided 1x1 downsample, conv1's node hands out the subsampled input
         # itself, and gets its gradient back compact: no zero-filled tensor of x's size is built for the GEMM to read.
+        # (bf16 only: in fp16 shortcut_subsample() declines and the downsample subsamples for itself.)
         sub = F_.shortcut_subsample(self.downsample, x)
         out, identity = F_.conv_bn_act(x, self.conv1, self.bn1, relu=True, passthrough=True, subsample=sub)
         out = F_.bn_act(self.conv2(out), self.bn2, relu=True)
