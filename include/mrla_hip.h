@@ -520,6 +520,22 @@ int mrla_conv1x1_wgrad_plan(int m, int k, int n, int dtype, int* out);
 int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                        void* stream);
 
+/* The same with the BatchNorm backward apply pass in front of it taken inside (two ADDITIVE symbols, MRLA_ABI_VERSION stays
+ * 5): for a convolution whose output xb goes straight into a BatchNorm(+ReLU), dy is not read but formed,
+ *     dy = e*dz + f*xb + h,  dz = g * [relu == 0 or sc*xb + sh > 0]      (mrla_bn_act_bwd's arithmetic and rounding)
+ * from g [m, n], the gradient arriving at the BatchNorm's output, xb [m, n], the BatchNorm's input, cb [n, 3] = (e, f, h)
+ * from mrla_bn_stats_bwd and sc, sh [n] (bnbuf rows 0, 1).  dy is multiplied as it is formed and written once to
+ * dy_out [m, n] for the input-gradient GEMM.  sc, sh and cb must be 16-byte aligned and dy_out must be neither g nor xb
+ * (MRLA_EINVAL otherwise; a partial overlap is not detected and not allowed).  dy_out, part and dw are bit-identical to
+ * mrla_bn_act_bwd(g, xb, ..., dy_out) followed by mrla_conv1x1_wgrad(dy_out, x, ...); part has the same rows.
+ * mrla_conv1x1_wgrad_bn_supported: 1 where mrla_conv1x1_wgrad_rows is positive and k is cut into one k-tile, or into two
+ * with n <= 512 (mrla_conv1x1_wgrad_plan: k / tile k); else MRLA_EUNSUPPORTED, from both: with more k-tiles every one of
+ * them forms dy again and the two passes are faster (measured, profiles/wgrad_bn.md). */
+int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype);
+int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb /*[n,3]*/, int relu,
+                          void* dy_out, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
+                          void* stream);
+
 /* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input
  * gradient): replaces what torch.autocast does in front of nn.Conv2d (resnet/train.py runs fp32; the bf16 configuration of
@@ -583,7 +599,8 @@ int mrla_bn_fwd(const void* x, const float* records, int rec_rows, float* amom, 
                 float* bnbuf, int relu, void* y, int b, int c, int h, int w, int dtype, int layout, void* stream);
 
 /* BatchNorm2d(+ReLU), backward:  [have_tmom == 0: mrla_bn_plane_dmoments(dy, x, ..., center = save_mean, tmom)] ->
- *   mrla_bn_stats_bwd(tmom, ..., centered = 1, rows) -> mrla_bn_act_bwd.
+ *   mrla_bn_stats_bwd(tmom, ..., centered = 1, rows) -> [dx != NULL: mrla_bn_act_bwd].
+ * dx == NULL: the sums and the constants only; mrla_conv1x1_wgrad_bn applies small's cb.
  * have_tmom != 0: tmom[rows, c, 2] was taken by the producer of dy (mrla_light_apply_bwd's pre_tmom).
  * small: [5, c] floats = cb[c,3] | dgamma | dbeta. */
 int mrla_bn_bwd(const void* dy, const void* x, const float* gamma, const float* bnbuf, float* tmom, int rows, int have_tmom,

@@ -6,6 +6,7 @@
 //                  -> partial sums [b * nsplit, c, 2]   (consumed by plain_bn_{fwd,bwd}_kernel with B = b*nsplit)
 //   nhwc_affine    forward y = relu?(sc*x + sh);  backward dx = e*dz + f*x + h
 #include <algorithm>
+#include <type_traits>
 
 #include "mrla_device.h"
 #include "mrla_kernels.h"
@@ -144,6 +145,7 @@ __global__ __launch_bounds__(kThreads) void nhwc_affine_kernel(const T* __restri
       else {
         const float dz = (!relu || z > 0.f) ? gv[i] : 0.f;
         y[i] = fmaf(ev[i], dz, fmaf(fv[i], xv[i], hv[i]));
+        if constexpr (sizeof(T) == 2 && !std::is_same<T, bf16_t>::value) y[i] = as_f32_result(y[i]);
       }
     }
     st16<T>(out + e0, y);
@@ -287,6 +289,7 @@ __global__ __launch_bounds__(kThreads) void nhwc_affine_flat_kernel(const T* __r
       else {
         const float dz = (!relu || z > 0.f) ? gv[i] : 0.f;
         y[i] = fmaf(cbv[3 * i], dz, fmaf(cbv[3 * i + 1], xv[i], cbv[3 * i + 2]));
+        if constexpr (sizeof(T) == 2 && !std::is_same<T, bf16_t>::value) y[i] = as_f32_result(y[i]);      // (fp16: see there)
       }
     }
     st16<T>(out + at, y);

@@ -734,6 +734,27 @@ int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
+int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype) {
+  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return conv1x1_wgrad_bn_supported(m, k, n);
+}
+
+int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                          void* dy_out, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
+                          void* stream) {
+  if (!g || !xb || !sc || !sh || !cb || !dy_out || !x || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype))
+    return MRLA_EINVAL;
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  // a lane reads 8 channels of sc, sh and 24 floats of cb as float4; dy_out is written while g and xb are still read
+  if (((uintptr_t)sc | (uintptr_t)sh | (uintptr_t)cb) & 15) return MRLA_EINVAL;
+  if (dy_out == g || dy_out == xb) return MRLA_EINVAL;
+  return launch_conv1x1_wgrad_bn(g, xb, sc, sh, cb, relu, dy_out, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype,
+                                 (hipStream_t)stream);
+}
+
 int mrla_weight_bank_refresh(const void* table, int entries, int max_tiles, void* stream) {
   if (!table || entries <= 0 || max_tiles <= 0) return MRLA_EINVAL;
   return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, MRLA_BF16, (hipStream_t)stream);

@@ -21,7 +21,21 @@
 //   * LDS reads and the barrier are inline asm / bare `s_barrier`: the compiler orders every LDS read it can see (and
 //     __syncthreads()) behind ALL outstanding LDS-DMA loads with `s_waitcnt vmcnt(0)`, which would serialise the
 //     stages (measured: 1 us per chunk whatever the depth).
+//
+// The BN form (mrla_conv1x1_wgrad_bn) takes the BatchNorm backward apply pass in front of this GEMM into it: dY is not
+// read but formed, dy = e*dz + f*xb + h with dz = g*[sc*xb + sh > 0] (nhwc_affine_flat_kernel<T, true>'s arithmetic and
+// rounding), from the gradient g arriving at the BatchNorm's output and the BatchNorm's input xb, the convolution's own
+// forward output.  g keeps dY's DMA route, xb gets a DMA tile of its own behind the stage's two (the largest stage,
+// 256 x 128, then makes 4 x 40 KB = all of the CU's LDS; one workgroup per CU is the plan anyway).  A lane's 16-byte DMA
+// piece covers the same 8 channels in every instruction and stage (the swizzle term depends on the thread alone), so it
+// keeps their 40 coefficients in registers, and after ITS OWN counted vmcnt says its pieces of a stage have landed --
+// that wait is what orders a wave's LDS reads behind its own DMA -- and before the barrier that publishes the stage, it
+// reads its pieces of g and xb back, rewrites g's in place with the rounded dy (zeros for rows >= M) and stores the same
+// 16 bytes to dy_out for the input-gradient GEMM (k-tile 0 only: the others get the store offset of a killed chunk, so
+// the number of stores in flight, which the counted waits include, is one constant).  The MFMAs then see exactly the
+// bytes mrla_bn_act_bwd would have written: bit-identical partial tiles.
 #include <algorithm>
+#include <type_traits>
 
 #include "conv1x1_elem.h"
 #include "mrla_device.h"
@@ -96,14 +110,40 @@ __device__ __forceinline__ unsigned wg_lds_addr(const void* p) {
   return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
 }
 
+// what the BN form reads and writes beside (g = dY's slot, X, part)
+struct WgBnArgs {
+  const void* xb;                 // [M, N] the BatchNorm's input
+  const float *cb, *sc, *sh;      // [N, 3] = (e, f, h); [N]; [N]
+  void* dy_out;                   // [M, N]
+  int relu;
+};
+
+__device__ __forceinline__ void wg_read16(u32x4& v, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
+}
+template <int OFF>
+__device__ __forceinline__ void wg_read16_at(u32x4& v, unsigned addr) {
+  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "n"(OFF));
+}
+__device__ __forceinline__ void wg_write16(unsigned addr, const u32x4& v) {
+  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
+}
+__device__ __forceinline__ void wg_fence16(u32x4& v, bool wait) {
+  if (wait) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory");
+  else asm volatile("" : "+v"(v) : : "memory");                 // rides on the wait of the piece fenced just before
+}
+
 // grid: tiles * splits workgroups (tiles = (N/TN)*(K/TK)) padded to a multiple of 8; 256 threads; LDS = ST * SB
-template <typename T, int TN, int TK, int ST, int PC>
+// BN: dY is g, and a stage is SB + YB bytes (the xb tile behind the two operand tiles)
+template <typename T, int TN, int TK, int ST, int PC, bool BN>
 __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, const T* __restrict__ X,
                                                    float* __restrict__ part, int M, int N, int K, int chunks_per_wg,
-                                                   int nsplits) {
+                                                   int nsplits, const WgBnArgs& bn) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef WgGeo<TN, TK, PC> G;
   constexpr int CPRY = TN / 8, CPRX = TK / 8;            // 16-byte chunks per tile row
+  constexpr int SB = G::SB + (BN ? G::YB : 0);           // bytes of one stage
+  static_assert(G::SB < 65536, "ds offset field");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -136,13 +176,18 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
     voffX[i] = (unsigned)(((size_t)c_begin * PC + row) * K * 2 + (k0 + ((cp ^ swz<CPRX>(row)) << 3)) * 2);
   }
   const unsigned advY = (unsigned)PC * N * 2, advX = (unsigned)PC * K * 2;
+  // BN: xb has dY's shape, so its pieces are fetched at dY's offsets (and are killed with them)
+  const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(BN ? bn.xb : nullptr), 0,
+                                                     BN ? (int)((size_t)M * N * 2) : 0, MRLA_WG_FLAGS);
   int issued = 0;
   auto issue = [&](int stage) {
-    unsigned char* sb = smem_raw + stage * G::SB;
+    unsigned char* sb = smem_raw + stage * SB;
     const unsigned kill = issued++ < nch ? 0u : 0x80000000u;      // past the range: out of bounds, no memory traffic
 #pragma unroll
     for (int i = 0; i < G::NIY; ++i) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rsY, (lds_void_ptr)(sb + (wave + kWgWaves * i) * 1024), 16, voffY[i] | kill, 0, 0, 0);
+      if constexpr (BN)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lds_void_ptr)(sb + G::SB + (wave + kWgWaves * i) * 1024), 16, voffY[i] | kill, 0, 0, 0);
       voffY[i] += advY;
     }
 #pragma unroll
@@ -169,14 +214,97 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
+  // ---- BN: this lane's 8 channels, their coefficients, and the rewrite of its own pieces of a stage ----
+  float cbv[BN ? 24 : 1], scv[BN ? 8 : 1], shv[BN ? 8 : 1];
+  unsigned tbase[BN ? G::NIY : 1], toff = 0;             // byte offsets of the pieces of chunk 0; chunks rewritten * advY
+  const auto rsO = __builtin_amdgcn_make_buffer_rsrc(BN ? bn.dy_out : nullptr, 0, BN ? (int)((size_t)M * N * 2) : 0,
+                                                     MRLA_WG_FLAGS);
+  const unsigned tlimit = (unsigned)((size_t)M * N * 2);
+  const unsigned skill = tk == 0 ? 0u : 0x80000000u;     // every k-tile rewrites its own copy; k-tile 0 stores dy_out
+  if constexpr (BN) {
+    // (the row term of the swizzle: instruction i adds 4 * i * (64 / CPRY) rows, a multiple of 8; a stage adds PC)
+    const int row0 = wave * (64 / CPRY) + lane / CPRY;
+    const int cch = n0 + (((lane % CPRY) ^ swz<CPRY>(row0)) << 3);
+#pragma unroll
+    for (int i = 0; i < G::NIY; ++i) tbase[i] = voffY[i];
+    const float4* c4 = reinterpret_cast<const float4*>(bn.cb + (size_t)cch * 3);
+    const float4* s4 = reinterpret_cast<const float4*>(bn.sc + cch);
+    const float4* h4 = reinterpret_cast<const float4*>(bn.sh + cch);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      const float4 v = c4[q];
+      cbv[4 * q] = v.x; cbv[4 * q + 1] = v.y; cbv[4 * q + 2] = v.z; cbv[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float4 u = s4[q], v = h4[q];
+      scv[4 * q] = u.x; scv[4 * q + 1] = u.y; scv[4 * q + 2] = u.z; scv[4 * q + 3] = u.w;
+      shv[4 * q] = v.x; shv[4 * q + 1] = v.y; shv[4 * q + 2] = v.z; shv[4 * q + 3] = v.w;
+    }
+    // used here, before the first DMA: the compiler's wait for these ordinary loads must not fall into the pipeline (it
+    // would be vmcnt(0)), and past this point the values are registers it cannot re-load
+#pragma unroll
+    for (int q = 0; q < 24; ++q) asm volatile("" : "+v"(cbv[q]));
+#pragma unroll
+    for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(scv[q]), "+v"(shv[q]));
+  }
+  const int relu = BN ? bn.relu : 0;
+  // the pieces this lane's DMA instructions dropped into the stage at byte offset sbo: g -> dy in place and to dy_out.
+  // Call it behind the counted vmcnt that covers the stage and in front of the barrier that publishes it.
+  auto rewrite = [&](unsigned sbo) {
+    u32x4 gq[G::NIY], xq[G::NIY];
+    const unsigned at = lds0 + sbo + wave * 1024 + lane * 16;
+#pragma unroll
+    for (int i = 0; i < G::NIY; ++i) {
+      wg_read16(gq[i], at + i * (kWgWaves * 1024));
+      wg_read16_at<G::SB>(xq[i], at + i * (kWgWaves * 1024));
+    }
+#pragma unroll
+    for (int i = 0; i < G::NIY; ++i) {
+      wg_fence16(gq[i], i == 0);
+      wg_fence16(xq[i], false);
+    }
+#pragma unroll
+    for (int i = 0; i < G::NIY; ++i) {
+      const unsigned off = tbase[i] + toff;
+      const bool live = off < tlimit;                    // a row at or past M: zeros for the MFMAs, no store
+      u32x4 o;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float gv[2] = {Elem16<T>::lo(gq[i][w]), Elem16<T>::hi(gq[i][w])};
+        const float xv[2] = {Elem16<T>::lo(xq[i][w]), Elem16<T>::hi(xq[i][w])};
+        float y[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int j = 2 * w + e;
+          const float z = fmaf(scv[j], xv[e], shv[j]);
+          const float dz = (!relu || z > 0.f) ? gv[e] : 0.f;
+          y[e] = fmaf(cbv[3 * j], dz, fmaf(cbv[3 * j + 1], xv[e], cbv[3 * j + 2]));
+          if constexpr (!std::is_same<T, bf16_t>::value) y[e] = as_f32_result(y[e]);      // (fp16: the apply pass's two roundings)
+        }
+        o[w] = live ? Elem16<T>::pack(y[0], y[1]) : 0u;
+      }
+      wg_write16(at + i * (kWgWaves * 1024), o);
+      __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (live ? off : 0x80000000u) | skill, 0, 0);
+    }
+    toff += advY;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+
   // ST stages rotate.  Chunks past the range are issued all the same, with an out-of-bounds offset (zeros from the
   // bounds check, no memory traffic): the wait counts stay compile-time constants.
   // The hand-over to the next chunk sits in front of the LAST k-step of a chunk, not between chunks: the wave waits
   // for its part of chunk c+1, meets the others at the barrier (after which chunk c-1's buffer is free for the DMA of
   // chunk c+ST-1), starts the LDS reads of chunk c+1's first k-step, and only then issues the MFMAs of chunk c's
   // last k-step -- barrier skew and LDS latency are covered by MFMAs already queued.
-  constexpr int KSN = PC / 16, NF = 2 * (G::BN + G::BK), NI = G::NIY + G::NIX;
-  static_assert(KSN % 2 == 0 && ST >= 3, "fragment double buffer / stages");
+  constexpr int KSN = PC / 16, NF = 2 * (G::BN + G::BK), NI = (BN ? 2 : 1) * G::NIY + G::NIX;
+  // BN: the NIY stores of a rewrite count in vmcnt like the loads (in order).  The wave's stream is
+  //   I(0) .. I(ST-2) S(0) | S(1) I(ST-1) | S(2) I(ST) | ...   (I = the DMA of a chunk, S = the stores of its rewrite),
+  // so when iteration c waits for I(c+1) there are ST-3 later I behind it, and S: ST-3 of them in the steady state,
+  // only S(0) in iteration 0 (none at all with three stages).  A smaller count only waits for more, so the constant
+  // is the least of these.
+  constexpr int W_NEXT = (ST - 3) * NI + (BN && ST > 3 ? G::NIY : 0);
+  static_assert(KSN % 2 == 0 && ST >= 3 && W_NEXT < 64 && (ST - 2) * NI < 64, "fragment double buffer / stages / vmcnt immediate");
   Frag fa[2][G::BN], fb[2][G::BK];
   auto read_step = [&](int buf, unsigned sbo, int ks) {
 #pragma unroll
@@ -194,12 +322,13 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 #pragma unroll
   for (int j = 0; j < ST - 1; ++j) issue(j);
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 2) * NI) : "memory");
+  if constexpr (BN) rewrite(0);
   __builtin_amdgcn_s_barrier();                         // (bare: __syncthreads() would drain vmcnt as well)
   asm volatile("" ::: "memory");
   read_step(0, 0, 0);
   int stage = 0, nxt = ST - 1;
   for (int c = 0; c < nch; ++c) {
-    const unsigned sbo = stage * G::SB;
+    const unsigned sbo = stage * SB;
     stage = stage + 1 == ST ? 0 : stage + 1;
 #pragma unroll
     for (int ks = 0; ks < KSN; ++ks) {
@@ -208,12 +337,13 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
       if (ks + 1 < KSN) {
         read_step(cur ^ 1, sbo, ks + 1);
       } else if (c + 1 < nch) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((ST - 3) * NI) : "memory");      // my part of chunk c+1 has landed
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W_NEXT) : "memory");      // my part of chunk c+1 has landed
+        if constexpr (BN) rewrite(stage * SB);
         __builtin_amdgcn_s_barrier();                   // everybody's has; everybody is done reading chunk c-1
         asm volatile("" ::: "memory");
         issue(nxt);
         nxt = nxt + 1 == ST ? 0 : nxt + 1;
-        read_step(0, stage * G::SB, 0);
+        read_step(0, stage * SB, 0);
       } else {
         pending = 0;
       }
@@ -245,7 +375,7 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_kernel(const bf
                                                                         const bf16_t* __restrict__ X,
                                                                         float* __restrict__ part, int M, int N, int K,
                                                                         int chunks_per_wg, int nsplits) {
-  conv1x1_wgrad_body<bf16_t, TN, TK, ST, PC>(dY, X, part, M, N, K, chunks_per_wg, nsplits);
+  conv1x1_wgrad_body<bf16_t, TN, TK, ST, PC, false>(dY, X, part, M, N, K, chunks_per_wg, nsplits, WgBnArgs{});
 }
 // the fp16 instances (a name of their own: see conv1x1_fwd_f16_kernel in conv1x1.hip)
 template <int TN, int TK, int ST, int PC>
@@ -253,7 +383,23 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_f16_kernel(cons
                                                                             const f16_t* __restrict__ X,
                                                                             float* __restrict__ part, int M, int N, int K,
                                                                             int chunks_per_wg, int nsplits) {
-  conv1x1_wgrad_body<f16_t, TN, TK, ST, PC>(dY, X, part, M, N, K, chunks_per_wg, nsplits);
+  conv1x1_wgrad_body<f16_t, TN, TK, ST, PC, false>(dY, X, part, M, N, K, chunks_per_wg, nsplits, WgBnArgs{});
+}
+// the BN form, both types
+template <int TN, int TK, int ST, int PC>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_bn_kernel(const bf16_t* __restrict__ g,
+                                                                           const bf16_t* __restrict__ X,
+                                                                           float* __restrict__ part, int M, int N, int K,
+                                                                           int chunks_per_wg, int nsplits, WgBnArgs bn) {
+  conv1x1_wgrad_body<bf16_t, TN, TK, ST, PC, true>(g, X, part, M, N, K, chunks_per_wg, nsplits, bn);
+}
+template <int TN, int TK, int ST, int PC>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_bn_f16_kernel(const f16_t* __restrict__ g,
+                                                                               const f16_t* __restrict__ X,
+                                                                               float* __restrict__ part, int M, int N,
+                                                                               int K, int chunks_per_wg, int nsplits,
+                                                                               WgBnArgs bn) {
+  conv1x1_wgrad_body<f16_t, TN, TK, ST, PC, true>(g, X, part, M, N, K, chunks_per_wg, nsplits, bn);
 }
 
 // dW[e] = sum over splits of part[s][e] in a fixed order: a workgroup takes 64 outputs, its 16 groups of 16 lanes take
@@ -323,10 +469,25 @@ WgPlan wgrad_plan(int M, int K, int N) {
 }
 
 template <int TN, int TK, int ST, int PC>
-int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st) {
+int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st,
+                const WgBnArgs* bn = nullptr) {
   typedef WgGeo<TN, TK, PC> G;
-  const size_t lds = (size_t)ST * G::SB;
   const dim3 grid((p.tiles * p.splits + 7) / 8 * 8), block(kWgWaves * kWave);
+  if (bn) {                        // dy is g; a stage carries the xb tile as well
+    const size_t lds = (size_t)ST * (G::SB + G::YB);
+    static_assert((size_t)ST * (G::SB + G::YB) <= 160 * 1024, "LDS of a CU");
+    if (dtype == MRLA_F16) {
+      if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_f16_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
+      hipLaunchKernelGGL((conv1x1_wgrad_bn_f16_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const f16_t*)dy, (const f16_t*)x,
+                         part, M, N, K, p.chunks_per_wg, p.splits, *bn);
+    } else {
+      if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
+      hipLaunchKernelGGL((conv1x1_wgrad_bn_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const bf16_t*)dy, (const bf16_t*)x,
+                         part, M, N, K, p.chunks_per_wg, p.splits, *bn);
+    }
+    return MRLA_OK;
+  }
+  const size_t lds = (size_t)ST * G::SB;
   if (dtype == MRLA_F16) {
     if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
     hipLaunchKernelGGL((conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const f16_t*)dy, (const f16_t*)x, part,
@@ -354,13 +515,26 @@ int conv1x1_wgrad_plan(int M, int K, int N, int* out) {
   return MRLA_OK;
 }
 
-int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
-                         hipStream_t st) {
+// The shapes the BN form takes: the plain form's where it is the faster route.  Every k-tile forms its own copy of dy, so
+// with T k-tiles the pair moves (2T + 2) N bytes through the fused form against (T + 4) N with the apply pass: less with one
+// k-tile, the same with two, more beyond -- and the kernel trace of the resnet50_mrlal step agrees (profiles/wgrad_bn.md
+// section 6): four and eight k-tiles (k = 1024, 2048) lose 11 to 27 us a launch, two k-tiles win where the repeated reads
+// stay in the cache (n <= 512) and are level (0.4 and 3.5 us of 118 and 66) at n = 1024 and 2048.
+int conv1x1_wgrad_bn_supported(int M, int K, int N) {
+  const WgPlan p = wgrad_plan(M, K, N);
+  if (!p.tiles) return MRLA_EUNSUPPORTED;
+  const int ktiles = K / p.tk;
+  return ktiles == 1 || (ktiles == 2 && N <= 512) ? 1 : MRLA_EUNSUPPORTED;
+}
+
+// bn [opt]: the BN form -- dy is then g, the gradient at the BatchNorm's output
+static int launch_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
+                        hipStream_t st, const WgBnArgs* bn) {
   const WgPlan p = wgrad_plan(M, K, N);
   if (!p.tiles || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
   int rc = MRLA_EUNSUPPORTED;
 #define MRLA_WG_TILE(A, B) \
-  if (p.tn == A && p.tk == B) rc = launch_tile<A, B, kWgStages, kPC>(p, dy, x, part, M, K, N, dtype, st);
+  if (p.tn == A && p.tk == B) rc = launch_tile<A, B, kWgStages, kPC>(p, dy, x, part, M, K, N, dtype, st, bn);
   MRLA_WG_TILE(64, 64) MRLA_WG_TILE(64, 128) MRLA_WG_TILE(64, 256) MRLA_WG_TILE(128, 64) MRLA_WG_TILE(128, 128)
   MRLA_WG_TILE(128, 256) MRLA_WG_TILE(256, 64) MRLA_WG_TILE(256, 128)
 #undef MRLA_WG_TILE
@@ -373,6 +547,19 @@ int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, i
   else
     hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<bf16_t>, dim3(NK / 64), dim3(256), 0, st, part, (bf16_t*)dw, p.splits, NK);
   return hip_status(hipGetLastError());
+}
+
+int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
+                         hipStream_t st) {
+  return launch_wgrad(dy, x, part, dw, dw_f32, M, K, N, dtype, st, nullptr);
+}
+
+int launch_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                            void* dy_out, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
+                            hipStream_t st) {
+  if (conv1x1_wgrad_bn_supported(M, K, N) != 1) return MRLA_EUNSUPPORTED;
+  const WgBnArgs bn{xb, cb, sc, sh, dy_out, relu};
+  return launch_wgrad(g, x, part, dw, dw_f32, M, K, N, dtype, st, &bn);
 }
 
 }  // namespace mrla

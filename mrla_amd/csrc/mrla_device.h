@@ -48,6 +48,15 @@ __device__ __forceinline__ void rebase_moments(float (&a)[M_N], float n, float p
   a[M_SO] += n * d_o;
 }
 
+// An fp32 result as the register holds it, for a value that is rounded to fp16 next.  Without it hipcc folds that rounding
+// into the fma that produced the value for SOME elements of a kernel (v_fma_mixlo/hi_f16: one rounding of the exact
+// result) and converts the fp32 result for others (v_cvt_pk_f16_f32: two roundings), as its unrolling falls: the same
+// arithmetic then differs in the last fp16 bit between the main and the tail loop of one kernel, and between two kernels
+// that must agree (the BatchNorm backward apply pass and its copy inside mrla_conv1x1_wgrad_bn).  No instruction.
+__device__ __forceinline__ float as_f32_result(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
 template <typename T> __device__ __forceinline__ float to_f(T v) { return static_cast<float>(v); }
 template <typename T> __device__ __forceinline__ T from_f(float v) { return static_cast<T>(v); }
 

@@ -204,6 +204,11 @@ int conv1x1_wgrad_rows(int M, int K, int N);
 int conv1x1_wgrad_plan(int M, int K, int N, int* out);
 int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
                          hipStream_t st);
+// ... with the BatchNorm backward apply dy = e*dz + f*xb + h formed inside it (g: the gradient at the BatchNorm's output)
+int conv1x1_wgrad_bn_supported(int M, int K, int N);
+int launch_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                            void* dy_out, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
+                            hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)

@@ -104,6 +104,7 @@ int mrla_bn_bwd(const void* dy, const void* x, const float* gamma, const float* 
     MRLA_TRY(mrla_bn_plane_dmoments(dy, x, bnbuf, bnbuf + C, bnbuf + 2 * C, relu, tmom, b, c, h, w, dtype, layout, stream));
   MRLA_TRY(mrla_bn_stats_bwd(tmom, gamma, bnbuf + 2 * C, bnbuf + 3 * C, bn_mode, 1, small, small + 3 * C, small + 4 * C, rows,
                              c, (int)((long)b * h * w / rows), stream));
+  if (!dx) return MRLA_OK;          // the consumer of small's cb forms dx itself (mrla_conv1x1_wgrad_bn)
   return mrla_bn_act_bwd(dy, x, bnbuf, bnbuf + C, small, relu, dx, b, c, h, w, dtype, layout, stream);
 }
 

@@ -65,6 +65,11 @@ SHORTCUT_ADDEND = True   # conv1's input-gradient GEMM takes the block's shortcu
 #                          scatter for the strided blocks, do the rest -- the same values, kept for A/B runs and tests.
 
 
+WGRAD_BN = True   # a 1x1 GEMM convolution + BatchNorm2d pair is one autograd node whose backward forms the BatchNorm's input
+#                   gradient inside the weight-gradient GEMM (mrla_conv1x1_wgrad_bn) instead of in an apply pass of its own.
+#                   False: the two nodes and the per-pass route -- the same values bit for bit, kept for A/B runs and tests.
+
+
 def _seq():
     return SEQUENCES and TIMER is None
 
@@ -1564,6 +1569,137 @@ class _SubsampleFn(torch.autograd.Function):
         return _scatter_subsample(g, ctx.shape, ctx.s[0], ctx.s[1], ctx.fmt), None, None
 
 
+class _SubCtx:
+    """What _Conv1x1Fn / _BnActFn ask of their autograd context, for _ConvBnFn to run their bodies as its two halves: the
+    tensors they save go into the real node's save_for_backward, everything else is plain attributes."""
+
+    def __init__(self):
+        self.saved_tensors, self.needs_input_grad = (), ()
+
+    def set_materialize_grads(self, flag):
+        pass
+
+    def save_for_backward(self, *tensors):
+        self.saved_tensors = tensors
+
+    def mark_non_differentiable(self, *tensors):
+        pass
+
+
+class _ConvBnFn(torch.autograd.Function):
+    """relu?(BatchNorm2d(conv1x1(x))) as ONE autograd node, so that its backward can hand the gradient arriving at the
+    BatchNorm's output straight to the weight-gradient GEMM (mrla_conv1x1_wgrad_bn): the BatchNorm backward apply pass
+    dy = e*dz + f*y + h is formed inside that GEMM, which writes dy once for the input-gradient GEMM -- the tensor between
+    the two halves never leaves this node.  The forward IS _Conv1x1Fn.forward followed by _BnActFn.forward, the backward is
+    theirs wherever the fused kernel does not apply (frozen weight, a gradient of another dtype or layout, an active
+    KernelTimer, WGRAD_BN off): same kernels, same order, same values.
+    Outputs: (out[, x']) or, deferred, (y, bnbuf[, x']) -- y the raw convolution output, bnbuf not differentiable; x' the
+    passthrough / subsample output of _Conv1x1Fn."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer, box, passthrough,
+                w16, w16t, sub):
+        ctx.set_materialize_grads(False)
+        ca, cb = _SubCtx(), _SubCtx()
+        # (gradients are off inside a forward: this call adds no node, it is _Conv1x1Fn's forward and nothing else.  Through
+        # .apply, not .forward(ca, ...): _Conv1x1Fn.apply is where the GEMM route is observed from outside, for this node too;
+        # the price is that ca is filled here with what _Conv1x1Fn.forward keeps for its backward)
+        res = _Conv1x1Fn.apply(x, w, bool(training), passthrough, w16, w16t, sub)
+        n, k = w.shape[0], x.shape[1]
+        ca.sub = tuple(sub) if (passthrough and sub is not None) else None
+        ca.wshape, ca.wstride, ca.wdtype = w.shape, w.stride(), w.dtype
+        ca.saved_tensors = (x, w16 if w16 is not None else w.reshape(n, k).contiguous(), w16t)
+        y, part = res[0], res[1]
+        out = _BnActFn.forward(cb, y, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer,
+                               part if part.numel() else None, box)
+        ctx.save_for_backward(*ca.saved_tensors, *cb.saved_tensors)       # x, w, w16t | y, gamma32, bnbuf
+        ca.saved_tensors = cb.saved_tensors = ()
+        ctx.ca, ctx.cb, ctx.defer, ctx.nthrough = ca, cb, bool(defer), len(res) - 2
+        if defer:
+            ctx.mark_non_differentiable(out[1])
+            return (y, out[1]) + tuple(res[2:])
+        return (out,) + tuple(res[2:]) if len(res) > 2 else out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, dy, *rest):
+        saved = ctx.saved_tensors
+        ca, cb = ctx.ca, ctx.cb
+        ca.saved_tensors, cb.saved_tensors = saved[:3], saved[3:]
+        try:
+            return _ConvBnFn._backward(ctx, dy, rest, saved)
+        finally:
+            # the unpacked tensors must not outlive this call on objects the node owns: the deferred output y and the
+            # passthrough x' carry this node as their grad_fn, and node -> ctx -> tensor -> node is a cycle no collector
+            # sees (the whole graph in front of it, its AccumulateGrad nodes and their streams included, would stay alive)
+            ca.saved_tensors = cb.saved_tensors = ()
+
+    @staticmethod
+    def _backward(ctx, dy, rest, saved):
+        d_through = rest[-1] if ctx.nthrough else None
+        ca, cb = ctx.ca, ctx.cb
+        ca.needs_input_grad = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        x, w, _ = saved[:3]
+        y, gamma32, bnbuf = saved[3:]
+        tail = (None,) * 12
+        if dy is None:             # only the shortcut carried a gradient
+            gx = _Conv1x1Fn.backward(ca, None, None, d_through)[0]
+            return (gx, None, None, None) + tail
+        n, k = w.shape
+        b, _, h, wd = x.shape
+        m = b * h * wd
+        lib, dt = L.load(), _DT[x.dtype]
+        g = dy if dy.is_contiguous(memory_format=_CL) else None
+        fused = (WGRAD_BN and TIMER is None and ctx.needs_input_grad[1] and g is not None and g.dtype == y.dtype
+                 and g.data_ptr() % 16 == 0 and cb.layout == L.NHWC and w.dtype == x.dtype
+                 and ca.wdtype in (x.dtype, torch.float32) and lib.mrla_conv1x1_wgrad_bn_supported(m, k, n, dt) == 1)
+        if not fused:              # the two backward passes as they are
+            dyc, dgamma, dbeta = _BnActFn.backward(cb, dy)[:3]
+            gx, gw = _Conv1x1Fn.backward(ca, dyc, None, d_through)[:2]
+            return (gx, gw, dgamma, dbeta) + tail
+        dev, st = x.device, _stream()
+        rows = cb.rows
+        handed = cb.box.take(g) if cb.box is not None else None           # (sum dz, sum dz*y) taken by the producer of dy
+        if handed is not None:
+            tmom, rows = handed
+        else:
+            tmom = torch.empty((rows, n, 2), dtype=torch.float32, device=dev)
+        small = torch.empty((5, n), dtype=torch.float32, device=dev)          # cb[n,3] | dgamma | dbeta
+        mode = L.BN_TRAIN if cb.training else L.BN_EVAL
+        if SEQUENCES:              # the sums (unless handed in) and the per-channel constants; no apply pass (dx = NULL)
+            _seq_call("mrla_bn_bwd", _ptr(g), _ptr(y), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, int(handed is not None),
+                      mode, cb.relu, _ptr(small), None, b, n, h, wd, dt, L.NHWC, st)
+        else:
+            if handed is None:
+                L.call("mrla_bn_plane_dmoments", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), cb.relu,
+                       _ptr(tmom), b, n, h, wd, dt, L.NHWC, st)
+            L.call("mrla_bn_stats_bwd", _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), mode, 1, _ptr(small),
+                   _ptr(small[3]), _ptr(small[4]), rows, n, m // rows, st)
+        prow = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
+        part = torch.empty((prow, n, k), dtype=torch.float32, device=dev)
+        gw = torch.empty((n, k), dtype=ca.wdtype, device=dev)
+        dyc = torch.empty_like(y)
+        L.call("mrla_conv1x1_wgrad_bn", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(small), cb.relu, _ptr(dyc),
+               _ptr(x), _ptr(part), _ptr(gw), m, k, n, dt, _DT[ca.wdtype], st)
+        ca.needs_input_grad = (ctx.needs_input_grad[0], False)
+        gx = _Conv1x1Fn.backward(ca, dyc, None, d_through)[0]
+        gw = _grad_like(gw, ca.wshape, ca.wstride)
+        return (gx, gw, small[3].to(cb.gdtype), small[4].to(cb.gdtype)) + tail
+
+
+def _conv_bn_fused(conv, bn, x, fused_bn):
+    """True when conv + bn on `x` (the GEMM's input) run as the one node _ConvBnFn: a bf16 input, the convolution on the
+    forward GEMM, a fused BatchNorm2d behind it, a weight that wants its gradient, and a shape mrla_conv1x1_wgrad_bn takes."""
+    if not (WGRAD_BN and TIMER is None and fused_bn and torch.is_grad_enabled() and conv.weight.requires_grad):
+        return False
+    if x.dtype != torch.bfloat16:      # fp16 keeps the two nodes, as the strided downsample does (conv1x1_applies): the
+        return False                   # kernel takes fp16 at the C ABI, the models' fp16 route is pinned pass by pass
+    b, k, h, w = x.shape
+    lib, m, n, dt = L.load(), b * h * w, conv.out_channels, _DT[x.dtype]
+    return lib.mrla_conv1x1_rows(m, k, n, dt) >= 0 and lib.mrla_conv1x1_wgrad_bn_supported(m, k, n, dt) == 1
+
+
 def _strided_1x1(conv):
     """nn.Conv2d 1x1, no padding, stride > 1 (resnet_mrla_light.py:196-199: the downsample branch of a stage's first block)."""
     return (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride != (1, 1)
@@ -1640,6 +1776,21 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
                 w16, w16t = held                     # the step's working copy in x's dtype and its transpose (WeightBank)
             else:
                 wt = wt.to(x.dtype)                  # what autocast does for the stock convolution (differentiable)
+        if _conv_bn_fused(conv, bn, x, fused_bn):
+            training = bn.training
+            momentum = bump_batch_counter(bn) if training else bn.momentum
+            box = _DeferredBnBox() if defer else None
+            through = passthrough and x.requires_grad
+            res = _ConvBnFn.apply(x, wt, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0,
+                                  bn.eps, relu, defer, box, through, w16, w16t, subsample if through else None)
+            res = res if isinstance(res, tuple) else (res,)
+            out = res[0]
+            if defer:
+                out._mrla_affine = (res[1][0], res[1][1])
+                out._mrla_bn_box = box
+            if not passthrough:
+                return out
+            return out, (res[-1] if through else second(x))
         if passthrough and torch.is_grad_enabled() and x.requires_grad:
             y, part, through = _Conv1x1Fn.apply(x, wt, bool(fused_bn and bn.training), True, w16, w16t, subsample)
             return bn_act(y, bn, relu, defer, pre_moments=part if part.numel() else None), through
