@@ -456,6 +456,55 @@ int mrla_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, const 
                           void* dx, int b, int c, int h, int w, int dtype, int layout, void* stream);
 
 /* =====================================================================================================
+ * Channel attention (SE / ECA) behind a BatchNorm2d: out = g[b,c] * BatchNorm2d(y), MRLA_NHWC only (reference call sites
+ * resnet/models/resnet_mrla_light.py:77-81 and :105-108 -- `out = self.bn3(out)`, `out = self.se(out)` / `self.eca(out)`;
+ * the gates are modules/se_module.py:19-23 and modules/eca_module.py:24-34).  3 passes over the activation forward,
+ * 5 backward; neither the BatchNorm's output nor an expanded gate or pool gradient exists.
+ *   forward : mrla_bn_plane_moments -> mrla_bn_stats_fwd -> mrla_bn_gate_pool -> [mrla_eca_gate_fwd | the caller's SE
+ *             network on pooled] -> mrla_bn_gate_fwd
+ *   backward: mrla_bn_plane_dmoments(relu = 0, center = save_mean) -> mrla_bn_gate_sums_bwd(q = NULL: dg) ->
+ *             [mrla_eca_gate_bwd | the caller's SE network: q = dpooled/hw] -> mrla_bn_gate_sums_bwd(q: tmom) ->
+ *             mrla_bn_stats_bwd(tmom, centered = 1, b rows of h*w pixels) -> mrla_bn_gate_bwd
+ * All [b,c] / [c] operands are float; those the streaming passes read (sc, sh, g, q, cb) and the activations must be
+ * 16-byte aligned (MRLA_EINVAL otherwise).  Every output element is written by the pass that owns it.
+ * ===================================================================================================== */
+/* 1 when these passes serve the shape; MRLA_EUNSUPPORTED for MRLA_NCHW and for channel counts that are not whole 16-byte
+ * vectors of `dtype` (every c % 64 == 0 is served) or more than 65535 images: the caller keeps the BatchNorm pass and the
+ * eager gate module. */
+int mrla_bn_gate_supported(int b, int c, int h, int w, int dtype, int layout);
+/* S[b,c] = sum_hw y and pooled[b,c] = sc[c]*S/hw + sh[c] (= the plane mean of the BatchNorm's output) from the partial rows
+ * amom[mrla_bn_moment_rows(), c, 2] of mrla_bn_plane_moments; pivot [opt, c]: the buffer that call recorded its shift in
+ * (the rows are then sums of y - pivot[c]).  Replaces `self.avg_pool(x)` (se_module.py:21, eca_module.py:28) and the
+ * read of bn3's output it needs. */
+int mrla_bn_gate_pool(const float* amom, const float* pivot, const float* sc, const float* sh, float* S, float* pooled,
+                      int b, int c, int h, int w, int layout, void* stream);
+/* g[b,c] = sigmoid(sum_j w[j] * pooled[b, c + j - (k-1)/2]), zero padded; k odd.  Replaces eca_module.py:31-32
+ * (`self.conv(...)` with its transposes, `self.sigmoid`). */
+int mrla_eca_gate_fwd(const float* pooled, const float* w, int k, float* g, int b, int c, void* stream);
+/* da = dg*g*(1-g);  q[b,c] = (sum_j w[j] * da[b, c - j + (k-1)/2]) / hw;  dw[j] = sum_{b,c} da[b,c] * pooled[b, c + j - (k-1)/2]
+ * (dw_part [b, k]: per-image partials, folded in a fixed order -- no atomics).  Replaces autograd's backward of
+ * eca_module.py:28-32 (sigmoid, Conv1d input and weight gradients, the adaptive pool's division by h*w). */
+int mrla_eca_gate_bwd(const float* dg, const float* g, const float* pooled, const float* w, int k, float* q, float* dw_part,
+                      float* dw, int b, int c, int hw, void* stream);
+/* From arows[mrla_bn_moment_rows(), c, 2] = mrla_bn_plane_dmoments(dout, y, center = mean, relu = 0), folded per image to
+ * (A1, A2) = (sum dout, sum dout*(y - mean)):
+ *   q == NULL: dg[b,c] = sum_hw dout*z = sc*A2 + (sc*mean + sh)*A1       (S, g, tmom unused)
+ *   q given  : tmom[b,c,:] = (g*A1 + hw*q, g*A2 + q*(S - hw*mean)) = (sum dz, sum dz*(y - mean)), dz = g*dout + q (dg unused)
+ * Replaces the [b,c] reduction of the multiply's backward (`x * y.expand_as(x)`, se_module.py:23 / eca_module.py:34), the
+ * expand-and-add of the pool's backward and the two reductions of bn3's backward over the full tensor. */
+int mrla_bn_gate_sums_bwd(const float* arows, const float* S, const float* g, const float* q, const float* sc,
+                          const float* sh, const float* mean, float* dg, float* tmom, int b, int c, int h, int w, int layout,
+                          void* stream);
+/* out = g[b,c] * (sc[c]*y + sh[c]): fp32 arithmetic, one rounding to dtype.  Replaces the normalisation half of bn3
+ * (resnet_mrla_light.py:102) and `x * y.expand_as(x)` (se_module.py:23, eca_module.py:34). */
+int mrla_bn_gate_fwd(const void* y, const float* sc, const float* sh, const float* g, void* out, int b, int c, int h, int w,
+                     int dtype, int layout, void* stream);
+/* dy = (e*g)*dout + f*y + (h + e*q) with cb[c,3] = (e, f, h) from mrla_bn_stats_bwd (mrla_bn_act_bwd's arithmetic and
+ * rounding).  Replaces the elementwise halves of the backward of the multiply, the pool and bn3. */
+int mrla_bn_gate_bwd(const void* dout, const void* y, const float* cb, const float* g, const float* q, void* dy, int b,
+                     int c, int h, int w, int dtype, int layout, void* stream);
+
+/* =====================================================================================================
  * The 1x1 stride-1 convolutions in front of those BatchNorms as an MFMA GEMM whose epilogue takes the BatchNorm
  * statistics (first half; reference call sites resnet/models/resnet_mrla_light.py:93-94
  * `conv1 -> bn1` and :100-101 `conv3 -> bn3`, both nn.Conv2d(kernel_size=1, stride=1, bias=False)).

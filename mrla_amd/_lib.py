@@ -84,6 +84,13 @@ SIGNATURES = {
     "mrla_bn_relu_pool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_relu_pool_dmoments": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_relu_pool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "mrla_bn_gate_supported": [_I] * 6,
+    "mrla_bn_gate_pool": [_P] * 6 + [_I] * 5 + [_P],
+    "mrla_eca_gate_fwd": [_P, _P, _I, _P, _I, _I, _P],
+    "mrla_eca_gate_bwd": [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P],
+    "mrla_bn_gate_sums_bwd": [_P] * 9 + [_I] * 5 + [_P],
+    "mrla_bn_gate_fwd": [_P, _P, _P, _P, _P] + [_I] * 6 + [_P],
+    "mrla_bn_gate_bwd": [_P, _P, _P, _P, _P, _P] + [_I] * 6 + [_P],
     "mrla_conv1x1_rows": [_I] * 4,
     "mrla_conv1x1_plan": [_I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_plan": [_I, _I, _I, _I, _P],

@@ -777,4 +777,68 @@ int mrla_reduce_rows2(const float* in1, float* out1, int rows1, int n1, const fl
   return launch_reduce_rows2(in1, out1, rows1, n1, in2, out2, rows2, n2, (hipStream_t)stream);
 }
 
+// ---- channel attention behind a BatchNorm2d (bn_gate_nhwc.hip) ----
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+// the [b,c] kernels index [b*c] rows and scale by h*w as ints
+static bool gate_rows_too_large(int b, int c, long hw) { return hw >= (1L << 31) || (long)b * c >= (1L << 30); }
+
+int mrla_bn_gate_supported(int b, int c, int h, int w, int dtype, int layout) {
+  if (bad_dims(b, c, h, w) || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (layout != MRLA_NHWC) return layout == MRLA_NCHW ? MRLA_EUNSUPPORTED : MRLA_EINVAL;
+  if (gate_rows_too_large(b, c, (long)h * w)) return MRLA_EUNSUPPORTED;
+  return bn_gate_supported(b, c, h * w, dtype);
+}
+
+int mrla_bn_gate_pool(const float* amom, const float* pivot, const float* sc, const float* sh, float* S, float* pooled,
+                      int b, int c, int h, int w, int layout, void* stream) {
+  if (!amom || !sc || !sh || !S || !pooled || bad_dims(b, c, h, w)) return MRLA_EINVAL;
+  if (layout != MRLA_NHWC) return layout == MRLA_NCHW ? MRLA_EUNSUPPORTED : MRLA_EINVAL;
+  if (gate_rows_too_large(b, c, (long)h * w)) return MRLA_EUNSUPPORTED;
+  return launch_bn_gate_pool(amom, pivot, sc, sh, S, pooled, b, c, h * w, (hipStream_t)stream);
+}
+
+int mrla_eca_gate_fwd(const float* pooled, const float* w, int k, float* g, int b, int c, void* stream) {
+  if (!pooled || !w || !g || b <= 0 || c <= 0 || k <= 0 || k % 2 == 0) return MRLA_EINVAL;
+  if (gate_rows_too_large(b, c, 1)) return MRLA_EUNSUPPORTED;
+  return launch_eca_gate_fwd(pooled, w, k, g, b, c, (hipStream_t)stream);
+}
+
+int mrla_eca_gate_bwd(const float* dg, const float* g, const float* pooled, const float* w, int k, float* q, float* dw_part,
+                      float* dw, int b, int c, int hw, void* stream) {
+  if (!dg || !g || !pooled || !w || !q || !dw_part || !dw || b <= 0 || c <= 0 || hw <= 0 || k <= 0 || k % 2 == 0)
+    return MRLA_EINVAL;
+  if (gate_rows_too_large(b, c, hw)) return MRLA_EUNSUPPORTED;
+  return launch_eca_gate_bwd(dg, g, pooled, w, k, q, dw_part, dw, b, c, hw, (hipStream_t)stream);
+}
+
+int mrla_bn_gate_sums_bwd(const float* arows, const float* S, const float* g, const float* q, const float* sc,
+                          const float* sh, const float* mean, float* dg, float* tmom, int b, int c, int h, int w, int layout,
+                          void* stream) {
+  if (!arows || !sc || !sh || !mean || bad_dims(b, c, h, w)) return MRLA_EINVAL;
+  if (q ? (!S || !g || !tmom) : !dg) return MRLA_EINVAL;
+  if (misaligned16(arows)) return MRLA_EINVAL;                 // (read as float2 pairs)
+  if (layout != MRLA_NHWC) return layout == MRLA_NCHW ? MRLA_EUNSUPPORTED : MRLA_EINVAL;
+  if (gate_rows_too_large(b, c, (long)h * w)) return MRLA_EUNSUPPORTED;
+  return launch_bn_gate_sums_bwd(arows, S, g, q, sc, sh, mean, dg, tmom, b, c, h * w, (hipStream_t)stream);
+}
+
+int mrla_bn_gate_fwd(const void* y, const float* sc, const float* sh, const float* g, void* out, int b, int c, int h, int w,
+                     int dtype, int layout, void* stream) {
+  if (!y || !sc || !sh || !g || !out || bad_dims(b, c, h, w) || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (misaligned16(y) || misaligned16(sc) || misaligned16(sh) || misaligned16(g) || misaligned16(out)) return MRLA_EINVAL;
+  const int rc = mrla_bn_gate_supported(b, c, h, w, dtype, layout);
+  if (rc != 1) return rc;
+  return launch_bn_gate_apply(y, nullptr, nullptr, sc, sh, g, nullptr, out, b, c, h * w, dtype, 0, (hipStream_t)stream);
+}
+
+int mrla_bn_gate_bwd(const void* dout, const void* y, const float* cb, const float* g, const float* q, void* dy, int b,
+                     int c, int h, int w, int dtype, int layout, void* stream) {
+  if (!dout || !y || !cb || !g || !q || !dy || bad_dims(b, c, h, w) || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (misaligned16(dout) || misaligned16(y) || misaligned16(cb) || misaligned16(g) || misaligned16(q) || misaligned16(dy))
+    return MRLA_EINVAL;
+  const int rc = mrla_bn_gate_supported(b, c, h, w, dtype, layout);
+  if (rc != 1) return rc;
+  return launch_bn_gate_apply(y, dout, cb, nullptr, nullptr, g, q, dy, b, c, h * w, dtype, 1, (hipStream_t)stream);
+}
+
 }  // extern "C"

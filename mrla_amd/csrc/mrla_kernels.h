@@ -262,4 +262,17 @@ int launch_nhwc_moments(const void* x, const void* dy, const float* sc, const fl
 int launch_nhwc_affine(const void* x, const void* dy, const float* a, const float* sc, const float* sh, int relu,
                        void* out, int B, int C, int HW, int dtype, int bwd, hipStream_t st);
 
+// bn_gate_nhwc.hip: channel attention (SE / ECA) behind a BatchNorm2d, channels_last
+int bn_gate_supported(int B, int C, int HW, int dtype);
+int launch_bn_gate_apply(const void* y, const void* go, const float* cb, const float* sc, const float* sh, const float* g,
+                         const float* q, void* out, int B, int C, int HW, int dtype, int bwd, hipStream_t st);
+int launch_bn_gate_pool(const float* amom, const float* pivot, const float* sc, const float* sh, float* S, float* pooled,
+                        int B, int C, int HW, hipStream_t st);
+int launch_eca_gate_fwd(const float* pooled, const float* w, int ks, float* g, int B, int C, hipStream_t st);
+int launch_eca_gate_bwd(const float* dg, const float* g, const float* pooled, const float* w, int ks, float* q,
+                        float* dw_part, float* dw, int B, int C, int HW, hipStream_t st);
+int launch_bn_gate_sums_bwd(const float* arows, const float* S, const float* g, const float* q, const float* sc,
+                            const float* sh, const float* mean, float* dg, float* tmom, int B, int C, int HW,
+                            hipStream_t st);
+
 }  // namespace mrla

@@ -70,6 +70,13 @@ WGRAD_BN = True   # a 1x1 GEMM convolution + BatchNorm2d pair is one autograd no
 #                   False: the two nodes and the per-pass route -- the same values bit for bit, kept for A/B runs and tests.
 
 
+CHANNEL_GATE = True   # a BatchNorm2d followed by channel attention (SE or ECA: resnet_mrla_light.py:77-81,105-108) is one autograd
+#                       node on the HIP passes of bn_gate_nhwc.hip: 3 passes over the activation forward and 5 backward, the
+#                       BatchNorm's output never stored (bn_gate).  False: bn_act, then the eager se_layer / eca_layer modules --
+#                       the same mathematics, kept for A/B runs and tests (and what NCHW tensors, both gates at once, another
+#                       norm layer or an active KernelTimer get either way).
+
+
 def _seq():
     return SEQUENCES and TIMER is None
 
@@ -1246,6 +1253,152 @@ def bn_act(x, bn, relu, defer=False, pre_moments=None):
     return torch.relu(y) if relu else y
 
 
+# ======================================================================================================
+# BatchNorm2d + channel attention (SE / ECA) -- resnet_mrla_light.py:77-81,105-108
+# ======================================================================================================
+class _BnGateFn(torch.autograd.Function):
+    """out = g * BatchNorm2d(y), g[b,c] = ECA or SE gate of the BatchNorm output's plane means ("Channel
+    attention").  kind 0: ECA, weights (w [1,1,k],); kind 1: SE, weights (W1 [c/r, c], W2 [c, c/r]), its two small
+    products as fp32 torch.mm on the [b,c] rows.  Everything that touches the activation is HIP: plane moments + apply
+    forward (3 passes), plane dmoments + apply backward (5 passes)."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, y, gamma, beta, running_mean, running_var, training, momentum, eps, kind, *weights):
+        _require_cuda(y, "bn + channel gate forward")
+        b, c, h, w = y.shape
+        hw = h * w
+        dt, dev, st = _DT[y.dtype], y.device, _stream()
+        lay = L.NHWC
+        gamma32, beta32 = _f32(gamma), _f32(beta)
+        rs = _RunningStats(running_mean, running_var, c, "bn + channel gate forward")
+        f32 = dict(dtype=torch.float32, device=dev)
+        bnbuf = torch.empty((4, c), **f32)                                   # sc, sh, save_mean, save_inv
+        rows = L.load().mrla_bn_moment_rows(b, c, h, w, lay)
+        amom = torch.empty((rows, c, 2), **f32)
+        pivot = torch.empty((c,), **f32) if training else None
+        sp = torch.empty((2, b, c), **f32)                                   # S | pooled
+        es = y.element_size()
+        # the plane sums are wanted in eval mode too: they are the pool
+        _call("mrla_bn_plane_moments", y.numel() * es, _ptr(y), _ptr(amom), _ptr(pivot), b, c, h, w, dt, lay, st)
+        _call("mrla_bn_stats_fwd", 0, _ptr(amom), _ptr(pivot), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
+              L.BN_TRAIN if training else L.BN_EVAL, float(momentum), float(eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
+              _ptr(bnbuf[2]), _ptr(bnbuf[3]), rows, c, b * hw // rows, st)
+        _call("mrla_bn_gate_pool", 0, _ptr(amom), _ptr(pivot), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(sp[0]), _ptr(sp[1]),
+              b, c, h, w, lay, st)
+        hid = None
+        if kind == 0:
+            wk = _f32(weights[0]).reshape(-1)
+            g = torch.empty((b, c), **f32)
+            _call("mrla_eca_gate_fwd", 0, _ptr(sp[1]), _ptr(wk), wk.numel(), _ptr(g), b, c, st)
+            saved_w = (wk,)
+        else:
+            w1, w2 = _f32(weights[0]), _f32(weights[1])
+            with torch.autocast("cuda", enabled=False):                      # (fp32 rows stay fp32 under autocast)
+                hid = torch.relu_(torch.mm(sp[1], w1.t()))                   # [b, c/r]
+                g = torch.sigmoid_(torch.mm(hid, w2.t()))
+            saved_w = (w1, w2, hid)
+        out = torch.empty_like(y)
+        _call("mrla_bn_gate_fwd", y.numel() * es * 2, _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(g), _ptr(out), b, c, h, w,
+              dt, lay, st)
+        rs.finish(training)
+        ctx.training, ctx.kind, ctx.rows = training, kind, rows
+        ctx.gdtype, ctx.wmeta = gamma.dtype, [(t.dtype, tuple(t.shape)) for t in weights]
+        ctx.save_for_backward(y, gamma32, bnbuf, sp, g, *saved_w)
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, do):
+        y, gamma32, bnbuf, sp, g, *saved_w = ctx.saved_tensors
+        b, c, h, w = y.shape
+        hw = h * w
+        dt, dev, st = _DT[y.dtype], y.device, _stream()
+        lay = L.NHWC
+        if do.dtype != y.dtype:
+            do = do.to(y.dtype)
+        do = _layout_of(do, lay)[1]
+        if do.data_ptr() % 16:                 # (a view at an odd storage offset: the passes move 16-byte vectors)
+            do = do.clone(memory_format=_CL)
+        f32 = dict(dtype=torch.float32, device=dev)
+        es = y.element_size()
+        arows = torch.empty((ctx.rows, c, 2), **f32)
+        dg = torch.empty((b, c), **f32)
+        tmom = torch.empty((b, c, 2), **f32)
+        small = torch.empty((5, c), **f32)                                   # cb[c,3] | dgamma | dbeta
+        sums = (_ptr(arows), _ptr(sp[0]), _ptr(g))
+        bn3 = (_ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]))
+        _call("mrla_bn_plane_dmoments", y.numel() * es * 2, _ptr(do), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), 0,
+              _ptr(arows), b, c, h, w, dt, lay, st)
+        _call("mrla_bn_gate_sums_bwd", 0, *sums, None, *bn3, _ptr(dg), None, b, c, h, w, lay, st)
+        if ctx.kind == 0:
+            wk = saved_w[0]
+            k = wk.numel()
+            q = torch.empty((b, c), **f32)
+            dwp = torch.empty((b + 1, k), **f32)                             # per-image partials | their sum
+            _call("mrla_eca_gate_bwd", 0, _ptr(dg), _ptr(g), _ptr(sp[1]), _ptr(wk), k, _ptr(q), _ptr(dwp), _ptr(dwp[b]), b, c,
+                  hw, st)
+            wgrads = (dwp[b],)
+        else:
+            w1, w2, hid = saved_w
+            with torch.autocast("cuda", enabled=False):
+                da = dg.mul_(g).mul_(1.0 - g)                                # through the sigmoid
+                dw2 = torch.mm(da.t(), hid)
+                dh = torch.mm(da, w2).mul_(hid > 0)
+                dw1 = torch.mm(dh.t(), sp[1])
+                q = torch.mm(dh, w1).div_(float(hw))
+            wgrads = (dw1, dw2)
+        _call("mrla_bn_gate_sums_bwd", 0, *sums, _ptr(q), *bn3, None, _ptr(tmom), b, c, h, w, lay, st)
+        cb = small[:3].view(c, 3)
+        _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]),
+              L.BN_TRAIN if ctx.training else L.BN_EVAL, 1, _ptr(cb), _ptr(small[3]), _ptr(small[4]), b, c, hw, st)
+        dy = torch.empty_like(y)
+        _call("mrla_bn_gate_bwd", y.numel() * es * 3, _ptr(do), _ptr(y), _ptr(cb), _ptr(g), _ptr(q), _ptr(dy), b, c, h, w, dt,
+              lay, st)
+        wg = tuple(t.reshape(shape).to(dtype) for t, (dtype, shape) in zip(wgrads, ctx.wmeta))
+        return (dy, small[3].to(ctx.gdtype), small[4].to(ctx.gdtype), None, None, None, None, None, None) + wg
+
+
+def bn_gate_applies(shape, dtype, channels_last, is_cuda, bn, se=None, eca=None):
+    """True when se?/eca?(bn(y)) for a `y` of that shape, dtype and layout is the one HIP node _BnGateFn: the switch is on,
+    no KernelTimer is active, `bn` is an nn.BatchNorm2d with affine and tracked statistics, exactly one of se / eca is given,
+    and y is a channels_last CUDA tensor of a shape mrla_bn_gate_supported takes."""
+    if not (CHANNEL_GATE and TIMER is None and (se is None) != (eca is None)):
+        return False
+    if not (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats):
+        return False
+    if not (is_cuda and len(shape) == 4 and dtype in _DT and channels_last):
+        return False
+    b, c, h, w = shape
+    if min(b, c, h, w) <= 0:
+        return False
+    return L.load().mrla_bn_gate_supported(b, c, h, w, _DT[dtype], L.NHWC) == 1
+
+
+def bn_gate(x, bn, se=None, eca=None, pre_moments=None):
+    """eca?(se?(bn(x))) -- `out = self.bn3(out)`, `out = self.se(out)`, `out = self.eca(out)` of resnet_mrla_light.py:102-108
+    -- for the raw output `x` of the convolution in front.  On the HIP node (bn_gate_applies) neither bn's output nor
+    anything else of x's size is stored between the passes; everything else is bn_act(x, bn) followed by the eager modules
+    (`pre_moments`: the producer's moment records, which only that route reads -- the HIP node takes the plane sums, which
+    are its pool as well)."""
+    if x.dim() == 4 and bn_gate_applies(tuple(x.shape), x.dtype, x.is_contiguous(memory_format=_CL), x.is_cuda, bn, se, eca) \
+            and x.data_ptr() % 16 == 0:
+        training = bn.training
+        momentum = bump_batch_counter(bn) if training else bn.momentum
+        if eca is not None:
+            kind, weights = 0, (eca.conv.weight,)
+        else:
+            kind, weights = 1, (se.fc[0].weight, se.fc[2].weight)
+        return _BnGateFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0, bn.eps,
+                               kind, *weights)
+    out = bn_act(x, bn, False, pre_moments=pre_moments)
+    if se is not None:
+        out = se(out)
+    if eca is not None:
+        out = eca(out)
+    return out
+
+
 class _BnReluPoolFn(torch.autograd.Function):
     """maxpool3x3/s2/p1(relu(BatchNorm2d(x))) on a channels_last tensor without the full-size intermediate
     (mrla_bn_relu_pool_*; resnet_mrla_light.py:220-222).  The statistics pass and the running-stat update are
@@ -1743,6 +1896,21 @@ def shortcut_subsample(downsample, x):
     return tuple(downsample[0].stride)
 
 
+def _gemm_weights(conv, x):
+    """(weight, w16, w16t) for _Conv1x1Fn / _ConvBnFn on the input `x`: the module's weight, and -- when it is an fp32 master
+    of a 16-bit `x` -- the step's working copy in x's dtype and its transpose from the WeightBank, or the weight cast as
+    autocast would cast it for the stock convolution (differentiable)."""
+    wt, w16, w16t = conv.weight, None, None
+    if wt.dtype != x.dtype:
+        book = current_bookkeeping()
+        held = book.bank.get(conv, x.dtype) if (book is not None and book.bank is not None and wt.dtype == torch.float32) else None
+        if held is not None:
+            w16, w16t = held
+        else:
+            wt = wt.to(x.dtype)
+    return wt, w16, w16t
+
+
 def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=None, presampled=False):
     """relu?(bn(conv(x))) -- resnet_mrla_light.py:93-94,100-101.  Eligible 1x1 convolutions run on the HIP GEMM, whose
     epilogue hands the train-mode BatchNorm its statistics (the moments pass over the output disappears); everything
@@ -1768,14 +1936,7 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
     if strided or conv1x1_applies(conv, x):
         if strided and not presampled:
             x = _SubsampleFn.apply(x, conv.stride[0], conv.stride[1])
-        wt, w16, w16t = conv.weight, None, None
-        if wt.dtype != x.dtype:
-            book = current_bookkeeping()
-            held = book.bank.get(conv, x.dtype) if (book is not None and book.bank is not None and wt.dtype == torch.float32) else None
-            if held is not None:
-                w16, w16t = held                     # the step's working copy in x's dtype and its transpose (WeightBank)
-            else:
-                wt = wt.to(x.dtype)                  # what autocast does for the stock convolution (differentiable)
+        wt, w16, w16t = _gemm_weights(conv, x)
         if _conv_bn_fused(conv, bn, x, fused_bn):
             training = bn.training
             momentum = bump_batch_counter(bn) if training else bn.momentum
@@ -1807,3 +1968,28 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
         return bn_act(torch.nn.functional.conv2d(xs, conv.weight), bn, relu, defer)
     out = bn_act(conv(x), bn, relu, defer)
     return (out, second(x)) if passthrough else out
+
+
+def conv_bn_gate(x, conv, bn, se=None, eca=None):
+    """eca?(se?(bn(conv(x)))) -- resnet_mrla_light.py:101-108 (conv3, bn3, then the block's channel attention).  Where the
+    BatchNorm + gate node applies to the convolution's output (bn_gate_applies) the convolution runs bare -- an eligible 1x1
+    on the HIP GEMM without moment records: the node's plane-moments pass, which it needs for the pool anyway, supplies the
+    statistics -- and bn_gate does the rest; otherwise conv_bn_act as without a gate, then the eager modules."""
+    if x.dim() == 4 and type(conv) is torch.nn.Conv2d:
+        cl = x.is_contiguous(memory_format=_CL)
+        ho = (x.shape[2] + 2 * conv.padding[0] - conv.dilation[0] * (conv.kernel_size[0] - 1) - 1) // conv.stride[0] + 1
+        wo = (x.shape[3] + 2 * conv.padding[1] - conv.dilation[1] * (conv.kernel_size[1] - 1) - 1) // conv.stride[1] + 1
+        odt = torch.get_autocast_dtype("cuda") if (x.is_cuda and torch.is_autocast_enabled("cuda")) else x.dtype
+        if bn_gate_applies((x.shape[0], conv.out_channels, ho, wo), odt, cl, x.is_cuda, bn, se, eca):
+            if conv1x1_applies(conv, x):
+                wt, w16, w16t = _gemm_weights(conv, x)
+                y, _ = _Conv1x1Fn.apply(x, wt, False, False, w16, w16t)
+            else:
+                y = conv(x)
+            return bn_gate(y, bn, se, eca)
+    out = conv_bn_act(x, conv, bn, relu=False)
+    if se is not None:
+        out = se(out)
+    if eca is not None:
+        out = eca(out)
+    return out

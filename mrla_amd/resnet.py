@@ -4,7 +4,9 @@ convolutions / BatchNorms stay stock PyTorch (MIOpen), as in the reference.
 
 Reference counterparts: resnet/models/resnet_mrla_light.py:47-250, resnet/models/resnet_mrla_base.py:55-283.
 SE / ECA options (off in every BASELINE config) keep their constructor arguments and
-state_dict keys and run as plain eager PyTorch modules on bn3's output (outside the accelerated path).
+state_dict keys.  On channels_last CUDA activations a block with one of them runs bn3 (bn2 in a BasicBlock) and the gate as
+one node on the HIP passes of bn_gate_nhwc.hip (functional.bn_gate / functional.CHANNEL_GATE); the se_layer / eca_layer
+modules below hold the parameters and are the eager route for everything else (NCHW, both gates at once, another norm layer).
 """
 
 import torch
@@ -24,7 +26,8 @@ def _conv1x1(cin, cout, stride=1):
 
 
 class se_layer(nn.Module):
-    """Squeeze-and-excitation gate (resnet/models/modules/se_module.py:9-24), eager PyTorch: not on the hot path."""
+    """Squeeze-and-excitation gate (resnet/models/modules/se_module.py:9-24).  Holds the parameters; `forward` is the eager
+    route -- the blocks go through functional.bn_gate, which reads `fc[0].weight` / `fc[2].weight` on the HIP route."""
 
     def __init__(self, channel, reduction=16):
         super().__init__()
@@ -38,7 +41,8 @@ class se_layer(nn.Module):
 
 
 class eca_layer(nn.Module):
-    """ECA gate (resnet/models/modules/eca_module.py:8-35), eager PyTorch: not on the hot path."""
+    """ECA gate (resnet/models/modules/eca_module.py:8-35).  Holds the parameters; `forward` is the eager route -- the blocks
+    go through functional.bn_gate, which reads `conv.weight` on the HIP route."""
 
     def __init__(self, channel, k_size=None):
         super().__init__()
@@ -87,18 +91,16 @@ class _BottleneckTrunk(nn.Module):
         sub = F_.shortcut_subsample(self.downsample, x)
         out, identity = F_.conv_bn_act(x, self.conv1, self.bn1, relu=True, passthrough=True, subsample=sub)
         out = F_.bn_act(self.conv2(out), self.bn2, relu=True)
-        if self.se is not None or self.eca is not None:     # channel attention reads bn3's output: nothing to defer
-            defer_bn3 = False
-        if callable(defer_bn3):                              # the predicate looks at conv3's output shape / layout only
-            b_, _, h_, w_ = out.shape
-            cl = out.is_contiguous(memory_format=torch.channels_last) and not out.is_contiguous()
-            defer_bn3 = defer_bn3(torch.empty((b_, self.conv3.out_channels, h_, w_), dtype=out.dtype, device="meta",
-                                              memory_format=torch.channels_last if cl else torch.contiguous_format))
-        out = F_.conv_bn_act(out, self.conv3, self.bn3, relu=False, defer=defer_bn3)
-        if self.se is not None:
-            out = self.se(out)
-        if self.eca is not None:
-            out = self.eca(out)
+        if self.se is not None or self.eca is not None:
+            # channel attention reads bn3's output, so nothing is deferred: bn3 and the gate are one node (F_.bn_gate)
+            out = F_.conv_bn_gate(out, self.conv3, self.bn3, self.se, self.eca)
+        else:
+            if callable(defer_bn3):                          # the predicate looks at conv3's output shape / layout only
+                b_, _, h_, w_ = out.shape
+                cl = out.is_contiguous(memory_format=torch.channels_last) and not out.is_contiguous()
+                defer_bn3 = defer_bn3(torch.empty((b_, self.conv3.out_channels, h_, w_), dtype=out.dtype, device="meta",
+                                                  memory_format=torch.channels_last if cl else torch.contiguous_format))
+            out = F_.conv_bn_act(out, self.conv3, self.bn3, relu=False, defer=defer_bn3)
         if self.downsample is not None:
             ds = self.downsample
             if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d):
@@ -166,11 +168,10 @@ class MRLA_BasicBlock(nn.Module):
         out = F_.bn_act(self.conv1(x), self.bn1, relu=True)
         # bn2's affine, the shortcut add and the ReLU all run inside the first MRLA pass (as bn3's do in the bottleneck)
         defer = layers.light_tail_is_fused(self.bn_mrla) and self.se is None and self.eca is None
-        out = F_.bn_act(self.conv2(out), self.bn2, relu=False, defer=defer)
-        if self.se is not None:
-            out = self.se(out)
-        if self.eca is not None:
-            out = self.eca(out)
+        if self.se is not None or self.eca is not None:      # bn2 and the gate are one node
+            out = F_.bn_gate(self.conv2(out), self.bn2, self.se, self.eca)
+        else:
+            out = F_.bn_act(self.conv2(out), self.bn2, relu=False, defer=defer)
         if self.downsample is not None:
             ds = self.downsample
             if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d):
