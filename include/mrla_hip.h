@@ -553,6 +553,26 @@ int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype
 int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int b, int h,
                             int w_, int sh, int sw, int dtype, void* stream);
 
+/* The forward in front of an EVAL-mode BatchNorm (+ReLU), for inference and for frozen stages (two ADDITIVE symbols: nothing
+ * above changes its arguments or its answers, MRLA_ABI_VERSION stays 5).  Reference call sites: resnet/models/
+ * resnet_mrla_light.py:93-94 `conv1 -> bn1 -> relu` and :196-199 (the downsample branch: 1x1 convolution + BatchNorm) under
+ * model.eval(), and mmdet's resnet_mrlal.py:358-367 (norm_eval: every BatchNorm of the training backbone in eval mode; stage
+ * 1 frozen).  A BatchNorm in eval mode is the fixed per-channel affine y = sc*z + sh, with sc, sh [n] fp32 as
+ * mrla_bn_stats_fwd(..., MRLA_BN_EVAL, ...) writes them (bnbuf rows 0, 1); the GEMM applies it on its way out:
+ *     y[m, n] = T( relu ? max(fma(sc[n], float(T(acc[m, n])), sh[n]), 0) : fma(sc[n], float(T(acc[m, n])), sh[n]) )
+ * -- the product rounded to the element type T exactly as mrla_conv1x1_fwd rounds it, then the expression and the rounding
+ * of mrla_bn_act_fwd's channels_last pass.  y is BIT-IDENTICAL to mrla_conv1x1_fwd(x, w, z, NULL, ...) followed by
+ * mrla_bn_act_fwd(z, sc, sh, relu, y, ..., MRLA_NHWC); the apply pass (1N read + 1N write) and z disappear.  Forward only:
+ * nothing here serves a backward pass, so a caller takes it only where nothing will be differentiated.
+ * mrla_conv1x1_fwd_affine_supported: 1 for every shape mrla_conv1x1_fwd takes (mrla_conv1x1_rows > 0) in MRLA_BF16 and
+ * MRLA_F16 -- the same planners, grids and kernel forms as that call -- else MRLA_EUNSUPPORTED.
+ * (As its siblings, the query answers MRLA_EINVAL for a non-positive m, k or n and for a dtype code that is none.)
+ * relu outside {0, 1}, m <= 0, a null pointer, or sc / sh not 16-byte aligned (the kernels read them as 16-byte vectors;
+ * bnbuf rows of a c % 64 == 0 BatchNorm are): MRLA_EINVAL, decided on the host before anything is launched.  No moment records (there is no statistics pass behind an eval-mode BatchNorm). */
+int mrla_conv1x1_fwd_affine_supported(int m, int k, int n, int dtype);
+int mrla_conv1x1_fwd_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int m, int k,
+                            int n, int dtype, void* stream);
+
 /* Weight gradient of the same convolution (the backward of the reference's nn.Conv2d(kernel_size=1) call sites above,
  * which the reference leaves to cuDNN):   dw[n, k] = sum_m dy[m, n] * x[m, k]
  *   dy: [m, n] and x: [m, k] channels_last activations (of `dtype`: MRLA_BF16 or MRLA_F16), dw: [n, k] (fp32 accumulation),

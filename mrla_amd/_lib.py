@@ -99,6 +99,8 @@ SIGNATURES = {
     "mrla_conv1x1_fwd_add": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "mrla_conv1x1_addend_supported": [_I] * 6,
     "mrla_conv1x1_fwd_addend": [_P, _P, _P, _P] + [_I] * 9 + [_P],
+    "mrla_conv1x1_fwd_affine_supported": [_I] * 4,
+    "mrla_conv1x1_fwd_affine": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_rows": [_I] * 4,
     "mrla_conv1x1_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_supported": [_I] * 4,

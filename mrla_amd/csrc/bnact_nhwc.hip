@@ -285,6 +285,9 @@ __global__ __launch_bounds__(kThreads) void nhwc_affine_flat_kernel(const T* __r
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
       const float z = fmaf(scv[i], xv[i], shv[i]);
+      // (forward: the fp32 z is rounded by st16, the runtime relu select between the fma and the conversion keeps hipcc from
+      // fusing them for fp16.  conv1x1_affine.h restates this expression and must produce the same bits -- mrla_conv1x1_fwd_affine,
+      // tests/test_conv1x1_affine_gpu.py; if this select ever becomes a template flag, wrap z in as_f32_result here as there.)
       if (!BWD) y[i] = relu ? fmaxf(z, 0.f) : z;
       else {
         const float dz = (!relu || z > 0.f) ? gv[i] : 0.f;

@@ -718,6 +718,22 @@ int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, vo
   return launch_conv1x1_addend(x, w, addend, y, m, k, n, b, h, w_, sh, sw, dtype, (hipStream_t)stream);
 }
 
+int mrla_conv1x1_fwd_affine_supported(int m, int k, int n, int dtype) {
+  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return conv1x1_affine_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
+}
+
+int mrla_conv1x1_fwd_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int m, int k,
+                            int n, int dtype, void* stream) {
+  if (!x || !w || !sc || !sh || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || (relu != 0 && relu != 1))
+    return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!conv1x1_affine_supported(m, k, n)) return MRLA_EUNSUPPORTED;
+  if (((uintptr_t)sc | (uintptr_t)sh) & 15) return MRLA_EINVAL;      // a thread reads 4 or 8 channels of sc, sh as 16-byte vectors
+  return launch_conv1x1_affine(x, w, sc, sh, relu, y, m, k, n, dtype, (hipStream_t)stream);
+}
+
 int mrla_conv1x1_wgrad_rows(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;

@@ -23,10 +23,15 @@
 //     K = 256 instance spilled); they are reduced across lanes and pixel-waves once at the end of the kernel and written
 //     as one partial row per workgroup;
 //   * the input-gradient use with the shortcut's gradient (conv1x1_fwd_addend_kernel, no moments): the store lane adds the
-//     addend's 16 bytes of the same pixel and channels to the piece it read back from the tile (conv1x1_addend.h).
+//     addend's 16 bytes of the same pixel and channels to the piece it read back from the tile (conv1x1_addend.h);
+//   * the inference use behind an eval-mode BatchNorm (conv1x1_fwd_affine_kernel, no moments, no addend): the store lane
+//     puts that piece through the BatchNorm's per-channel affine and ReLU (conv1x1_affine.h).  A lane stores the same 8
+//     channels of every row; the wave's 64 + 64 fp32 coefficients sit in the 16 padding bytes behind the 32 rows of its
+//     output tile (32 x 16 B = 512 B, exactly them) and are read back per block, so no register lives across the MFMAs.
 #include <algorithm>
 
 #include "conv1x1_addend.h"
+#include "conv1x1_affine.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -40,13 +45,15 @@ constexpr int kOutTileB = 32 * kOutRowB;
 // channel of accumulator register `reg` inside its 32-channel tile, for lane half h
 __device__ __forceinline__ int acc_channel(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-template <typename T, int KS, bool MOM, int NW, bool ADD>
+template <typename T, int KS, bool MOM, int NW, bool ADD, bool AFF = false>
 __device__ __forceinline__ void conv1x1_fwd_body(
     const T* __restrict__ X, const T* __restrict__ W, T* Y, float* __restrict__ part,
-    int M, int N, int NS, int WN, int rows_total, const T* A, const AddendGeo& ag) {
+    int M, int N, int NS, int WN, int rows_total, const T* A, const AddendGeo& ag,
+    const float* __restrict__ sc = nullptr, const float* __restrict__ sh = nullptr, int relu = 0) {
   typedef Elem16<T> E;
   typedef typename E::x8 x8;
   static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
+  static_assert(!(AFF && (MOM || ADD)), "the affine form is the plain forward of inference: no records, no addend");
   constexpr int K = KS * 16;
   constexpr int ROWB = K * 2 + 16;                   // padded LDS row of W, bytes
   constexpr int KC = KS < 16 ? KS : 16;              // k-steps whose X fragments are in registers at a time
@@ -69,6 +76,15 @@ __device__ __forceinline__ void conv1x1_fwd_body(
     }
   }
   __syncthreads();
+
+  if (AFF) {
+    // the wave's coefficients into the padding of its output tile: row 4*piece + q holds, for the 8 channels of 16-byte
+    // piece `piece`, sc[0..3], sc[4..7], sh[0..3], sh[4..7] (q = 0..3).  Wave-private, like the tile: no barrier.
+    if (lane < 32) {
+      const float* src = ((lane & 2) ? sh : sc) + n_slice0 + wn * 64 + (lane >> 2) * 8 + (lane & 1) * 4;
+      *reinterpret_cast<u32x4*>(otile + lane * kOutRowB + 128) = *reinterpret_cast<const u32x4*>(src);
+    }
+  }
 
   // moments about a pivot (this wave's first output of the channel), see conv1x1_wide.hip; taken on the store lanes:
   // a lane keeps the 8 channels of ITS 16-byte piece of the output lines, the same piece for every block of the wave
@@ -159,11 +175,21 @@ __device__ __forceinline__ void conv1x1_fwd_body(
 #pragma unroll
         for (int j = 0; j < 4; ++j) { pv[2 * j] = E::lo(p0[j]); pv[2 * j + 1] = E::hi(p0[j]); }
       }
+      float sc8[8], sh8[8];
+      if (AFF) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const u32x4 c = *reinterpret_cast<const u32x4*>(otile + (piece * 4 + q) * kOutRowB + 128);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) (q < 2 ? sc8 : sh8)[(q & 1) * 4 + j] = __uint_as_float(c[j]);
+        }
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int pr = i * 8 + px;
         u32x4 v = *reinterpret_cast<const u32x4*>(otile + pr * kOutRowB + piece * 16);
         if (ADD) v = addend_add8<T>(v, av[i]);
+        if (AFF) v = affine8<T>(v, sc8, sh8, relu);
         const bool lv = blk * 32 + pr < M;
         if (lv) *reinterpret_cast<u32x4*>(ybase + (size_t)pr * N) = v;
         if (MOM) {
@@ -260,6 +286,23 @@ __global__ __launch_bounds__(NW * kWave) void conv1x1_fwd_f16_addend_kernel(
     const f16_t* __restrict__ X, const f16_t* __restrict__ W, const f16_t* A, f16_t* Y, int M, int N, int NS, int WN,
     AddendGeo ag) {
   conv1x1_fwd_body<f16_t, KS, false, NW, true>(X, W, Y, nullptr, M, N, NS, WN, 0, A, ag);
+}
+
+// y = T(relu?(sc * T(x w^T) + sh)): the forward in front of an eval-mode BatchNorm.  Names of their own, as above.
+// Held to the waves per SIMD the plain instances (MOM = false) they are launched in place of compile to: the affine must not
+// cost the register allocation a wave.
+template <int KS> constexpr int kAffWaves = KS == 4 ? 5 : KS == 8 ? 4 : 2;
+template <int KS, int NW>
+__global__ __launch_bounds__(NW * kWave, kAffWaves<KS>) void conv1x1_fwd_affine_kernel(
+    const bf16_t* __restrict__ X, const bf16_t* __restrict__ W, const float* __restrict__ sc, const float* __restrict__ sh,
+    int relu, bf16_t* __restrict__ Y, int M, int N, int NS, int WN) {
+  conv1x1_fwd_body<bf16_t, KS, false, NW, false, true>(X, W, Y, nullptr, M, N, NS, WN, 0, nullptr, AddendGeo(), sc, sh, relu);
+}
+template <int KS, int NW>
+__global__ __launch_bounds__(NW * kWave, kAffWaves<KS>) void conv1x1_fwd_f16_affine_kernel(
+    const f16_t* __restrict__ X, const f16_t* __restrict__ W, const float* __restrict__ sc, const float* __restrict__ sh,
+    int relu, f16_t* __restrict__ Y, int M, int N, int NS, int WN) {
+  conv1x1_fwd_body<f16_t, KS, false, NW, false, true>(X, W, Y, nullptr, M, N, NS, WN, 0, nullptr, AddendGeo(), sc, sh, relu);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -391,6 +434,47 @@ int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void
   {                                                                                                                   \
     if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_addend_kernel, f16_t, KS, NWV)                                      \
     else CALL_T(conv1x1_fwd_addend_kernel, bf16_t, KS, NWV)                                                           \
+  }
+#define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
+  switch (K) {
+    case 64:  CALL(4) break;
+    case 128: CALL(8) break;
+    case 256:
+      if (g.NW != 8) return MRLA_EUNSUPPORTED;
+      CALL_W(16, 8)
+      break;
+    default: return MRLA_EUNSUPPORTED;
+  }
+#undef CALL
+#undef CALL_W
+#undef CALL_T
+  return hip_status(hipGetLastError());
+}
+
+// The same dispatch as launch_conv1x1_fwd (same planners, grids and LDS sizes) with the eval-mode BatchNorm's affine
+// (+ReLU) applied to the rounded product on its way out (conv1x1_affine.h).  No moment records.
+int conv1x1_affine_supported(int M, int K, int N) { return conv1x1_rows(M, K, N) > 0; }
+
+int launch_conv1x1_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
+                          int N, int dtype, hipStream_t st) {
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (conv1x1_wide_rows(M, K, N) > 0) return launch_conv1x1_wide_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  GemmGeo g;
+  if (!conv1x1_geo(&g, M, K, N)) {
+    if (!conv1x1_kstream_supported(M, K, N)) return MRLA_EUNSUPPORTED;
+    return launch_conv1x1_kstream_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  }
+  const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
+#define CALL_T(KERNEL, T, KS, NWV)                                                                                    \
+  {                                                                                                                   \
+    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;             \
+    hipLaunchKernelGGL((KERNEL<KS, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, sc, sh, relu, (T*)y, M, N, \
+                       g.NS, g.WN);                                                                                   \
+  }
+#define CALL_W(KS, NWV)                                                                                               \
+  {                                                                                                                   \
+    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_affine_kernel, f16_t, KS, NWV)                                      \
+    else CALL_T(conv1x1_fwd_affine_kernel, bf16_t, KS, NWV)                                                           \
   }
 #define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
   switch (K) {

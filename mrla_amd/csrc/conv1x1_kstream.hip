@@ -18,6 +18,9 @@
 //     filling and draining its pipeline);
 //   * LDS reads are inline asm with explicit lgkmcnt fences, the barrier is a bare s_barrier and the DMA waits are
 //     constant-count vmcnt (see conv1x1_wgrad.hip: the compiler would drain all DMA stages at every LDS access);
+//   * the inference use behind an eval-mode BatchNorm (the *_affine_kernel entries, AFF; no moments, no addend): the thread
+//     that copies a 16-byte piece out puts it through the BatchNorm's per-channel affine and ReLU (conv1x1_affine.h); it
+//     keeps the same 8 channels for all its rows, and fetches their 8 + 8 coefficients once the accumulation is over;
 //   * the fp32 tile is rounded once, transposed to pixel-major 16-byte pieces with v_permlane32_swap (as
 //     conv1x1_wide.hip) through the (then idle) stage memory and leaves as whole rows.
 // These products need 0.5 - 2 PFLOP/s to run at the HBM rate (N*K/(N+K) = 100 - 400 flop per byte), so unlike their
@@ -25,6 +28,7 @@
 #include <algorithm>
 
 #include "conv1x1_addend.h"
+#include "conv1x1_affine.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -77,12 +81,24 @@ __device__ __forceinline__ int ks_oswz(int row) { return row & 7; }            /
 // A may alias Y -- a thread reads exactly the bytes it overwrites).  Its TM / RPI addend loads are issued together, ahead
 // of the LDS reads: the accumulators are dead here, and a dependent load in front of every store would put the load
 // latency into the tile epilogue once per row.
-template <typename T, int TM, int TN, bool MOM, bool ADD>
+// AFF (the inference use, never with MOM or ADD): the staged values go through the affine of the thread's eight channels.
+struct KsAffine { float sc[8], sh[8]; int relu; };
+
+// the coefficients of the piece thread `threadIdx.x` copies out of a [.][TN] tile at channel n0
+template <int TN>
+__device__ __forceinline__ void ks_affine_load(KsAffine& af, const float* __restrict__ sc, const float* __restrict__ sh,
+                                               int relu, int n0) {
+  affine_load8(af.sc, af.sh, sc, sh, n0 + (int)(threadIdx.x % (TN / 8)) * 8);
+  af.relu = relu;
+}
+
+template <typename T, int TM, int TN, bool MOM, bool ADD, bool AFF = false>
 __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned lds0, T* Y,
                                               float* __restrict__ mom_part, int M, int N, int m0, int n0, int tile,
-                                              const T* A, const AddendGeo& ag) {
+                                              const T* A, const AddendGeo& ag, const KsAffine& af = KsAffine()) {
   typedef Elem16<T> E;
   static_assert(!(MOM && ADD), "the moment records are those of the GEMM's own outputs");
+  static_assert(!(AFF && (MOM || ADD)), "the affine form is the plain forward of inference: no records, no addend");
   constexpr int CPR = TN / 8, RPI = (kKsWaves * kWave) / CPR;
   const int srow = threadIdx.x / CPR, chunk = threadIdx.x % CPR;
   u32x4 av[ADD ? TM / RPI : 1];
@@ -112,6 +128,7 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
     ks_read16(v, lds0 + row * (TN * 2) + ((chunk ^ ks_oswz(row)) << 4));
     ks_fence<0>(v, true);
     if (ADD) v = addend_add8<T>(v, av[i]);
+    if (AFF) v = affine8<T>(v, af.sc, af.sh, af.relu);
     if (m0 + row < M) {
       *reinterpret_cast<u32x4*>(Y + (size_t)(m0 + row) * N + n0 + chunk * 8) = v;
       if (MOM) {
@@ -149,10 +166,12 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
   }
 }
 
-template <typename T, int WN, int PB, bool MOM, bool ADD>
+template <typename T, int WN, int PB, bool MOM, bool ADD, bool AFF = false>
 __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, const T* __restrict__ W, T* Y,
                                                      float* __restrict__ mom_part, int M, int N, int K, int tiles_m,
-                                                     int groups_n, const T* A, const AddendGeo& ag) {
+                                                     int groups_n, const T* A, const AddendGeo& ag,
+                                                     const float* __restrict__ sc = nullptr,
+                                                     const float* __restrict__ sh = nullptr, int relu = 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Elem16<T> E;
   typedef typename E::x8 ks_x8;
@@ -267,6 +286,8 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+  KsAffine af;
+  if (AFF) ks_affine_load<G::TN>(af, sc, sh, relu, n0);       // (in flight while the tile is rounded and staged)
 
   // ---- epilogue: round once, 16-byte pieces of each pixel's row, staged in LDS, whole rows out ----
   // acc[p][cb]: lane = pixel r of block p; register e = channel 8*(e/4) + 4*h + e%4 of the 32-channel block cb
@@ -297,7 +318,7 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<T, G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
+  ks_store_tile<T, G::TM, G::TN, MOM, ADD, AFF>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag, af);
 #endif
 }
 
@@ -321,6 +342,28 @@ __global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_f16_kernel
   conv1x1_kstream_body<f16_t, WN, PB, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
 }
 
+// the forward in front of an eval-mode BatchNorm: y = T(relu?(sc * T(x w^T) + sh)) (names of their own, as above)
+template <int WN, int PB>
+__global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_affine_kernel(const bf16_t* __restrict__ X,
+                                                                                    const bf16_t* __restrict__ W,
+                                                                                    const float* __restrict__ sc,
+                                                                                    const float* __restrict__ sh, int relu,
+                                                                                    bf16_t* Y, int M, int N, int K,
+                                                                                    int tiles_m, int groups_n) {
+  conv1x1_kstream_body<bf16_t, WN, PB, false, false, true>(X, W, Y, nullptr, M, N, K, tiles_m, groups_n, nullptr, AddendGeo(),
+                                                           sc, sh, relu);
+}
+template <int WN, int PB>
+__global__ __launch_bounds__(kKsWaves* kWave, 4) void conv1x1_kstream_f16_affine_kernel(const f16_t* __restrict__ X,
+                                                                                        const f16_t* __restrict__ W,
+                                                                                        const float* __restrict__ sc,
+                                                                                        const float* __restrict__ sh, int relu,
+                                                                                        f16_t* Y, int M, int N, int K,
+                                                                                        int tiles_m, int groups_n) {
+  conv1x1_kstream_body<f16_t, WN, PB, false, false, true>(X, W, Y, nullptr, M, N, K, tiles_m, groups_n, nullptr, AddendGeo(),
+                                                          sc, sh, relu);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The 256 x 256 tile (round 3, second form).  In the kernel above a wave owns 64 channels x 64 pixels: one ds_read_b128
 // per MFMA, and since the CU's LDS port delivers one such read in the time its four matrix pipes take for four MFMAs, LDS
@@ -335,10 +378,12 @@ struct Ks256 {
   static constexpr int kLds = ST * SB;                  // 128 KB: also exactly the 16-bit output tile
 };
 
-template <typename T, bool MOM, bool ADD>
+template <typename T, bool MOM, bool ADD, bool AFF = false>
 __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X, const T* __restrict__ W, T* Y,
                                                         float* __restrict__ mom_part, int M, int N, int K, int tiles_m,
-                                                        int groups_n, const T* A, const AddendGeo& ag) {
+                                                        int groups_n, const T* A, const AddendGeo& ag,
+                                                        const float* __restrict__ sc = nullptr,
+                                                        const float* __restrict__ sh = nullptr, int relu = 0) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Elem16<T> E;
   typedef typename E::x8 ks_x8;
@@ -457,6 +502,8 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (dummy chunks past the end: no data, but their LDS writes)
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
+  KsAffine af;
+  if (AFF) ks_affine_load<G::TN>(af, sc, sh, relu, n0);       // (in flight while the tile is rounded and staged)
 
   // ---- epilogue: as above (round once, v_permlane32_swap to 16-byte pieces, whole rows out) ----
 #pragma unroll
@@ -484,7 +531,7 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-  ks_store_tile<T, G::TM, G::TN, MOM, ADD>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag);
+  ks_store_tile<T, G::TM, G::TN, MOM, ADD, AFF>(smem_raw, lds0, Y, mom_part, M, N, m0, n0, tile, A, ag, af);
 #endif
 }
 
@@ -505,6 +552,25 @@ __global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_f16_ker
                                                                                    int K, int tiles_m, int groups_n,
                                                                                    const f16_t* A, AddendGeo ag) {
   conv1x1_kstream256_body<f16_t, MOM, ADD>(X, W, Y, mom_part, M, N, K, tiles_m, groups_n, A, ag);
+}
+
+__global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_affine_kernel(const bf16_t* __restrict__ X,
+                                                                                      const bf16_t* __restrict__ W,
+                                                                                      const float* __restrict__ sc,
+                                                                                      const float* __restrict__ sh, int relu,
+                                                                                      bf16_t* Y, int M, int N, int K,
+                                                                                      int tiles_m, int groups_n) {
+  conv1x1_kstream256_body<bf16_t, false, false, true>(X, W, Y, nullptr, M, N, K, tiles_m, groups_n, nullptr, AddendGeo(), sc,
+                                                      sh, relu);
+}
+__global__ __launch_bounds__(kKsWaves* kWave, 2) void conv1x1_kstream256_f16_affine_kernel(const f16_t* __restrict__ X,
+                                                                                          const f16_t* __restrict__ W,
+                                                                                          const float* __restrict__ sc,
+                                                                                          const float* __restrict__ sh,
+                                                                                          int relu, f16_t* Y, int M, int N,
+                                                                                          int K, int tiles_m, int groups_n) {
+  conv1x1_kstream256_body<f16_t, false, false, true>(X, W, Y, nullptr, M, N, K, tiles_m, groups_n, nullptr, AddendGeo(), sc,
+                                                     sh, relu);
 }
 
 struct KsPlan {
@@ -590,6 +656,38 @@ int ks_dispatch(const void* x, const void* w, void* y, float* part, int M, int K
   return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, dtype, st, a, ag) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
 }
 
+template <int WN, int PB>
+int ks_launch_affine(const KsPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M,
+                     int K, int N, int dtype, hipStream_t st) {
+  typedef KsGeo<WN, PB> G;
+  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_f16_affine_kernel<WN, PB>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream_f16_affine_kernel<WN, PB>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
+                       sc, sh, relu, (f16_t*)y, M, N, K, p.tiles_m, p.groups_n);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_affine_kernel<WN, PB>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_kstream_affine_kernel<WN, PB>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       sc, sh, relu, (bf16_t*)y, M, N, K, p.tiles_m, p.groups_n);
+  }
+  return hip_status(hipGetLastError());
+}
+
+int ks_launch256_affine(const KsPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y,
+                        int M, int K, int N, int dtype, hipStream_t st) {
+  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_f16_affine_kernel), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL(conv1x1_kstream256_f16_affine_kernel, grid, block, Ks256::kLds, st, (const f16_t*)x, (const f16_t*)w,
+                       sc, sh, relu, (f16_t*)y, M, N, K, p.tiles_m, p.groups_n);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_affine_kernel), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL(conv1x1_kstream256_affine_kernel, grid, block, Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
+                       sc, sh, relu, (bf16_t*)y, M, N, K, p.tiles_m, p.groups_n);
+  }
+  return hip_status(hipGetLastError());
+}
+
 }  // namespace
 
 int conv1x1_kstream_supported(int M, int K, int N) { return ks_plan(M, K, N).wn ? 1 : 0; }
@@ -605,6 +703,18 @@ int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, i
 int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
                                   int wd, int sh, int sw, int dtype, hipStream_t st) {
   return ks_dispatch(x, w, y, nullptr, M, K, N, dtype, st, addend, make_addend_geo(b, h, wd, sh, sw));
+}
+
+// y = T(relu?(sc * T(x w^T) + sh)): the plain forward's plan, grid and LDS, the affine applied by the threads that copy the tile out
+int launch_conv1x1_kstream_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
+                                  int N, int dtype, hipStream_t st) {
+  const KsPlan p = ks_plan(M, K, N);
+  if (!p.wn || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
+  if (p.big) return ks_launch256_affine(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  if (p.wn == 4) return p.pb == 2 ? ks_launch_affine<4, 2>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st)
+                                  : ks_launch_affine<4, 1>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  return p.pb == 2 ? ks_launch_affine<2, 2>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st)
+                   : ks_launch_affine<2, 1>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
 }
 
 }  // namespace mrla

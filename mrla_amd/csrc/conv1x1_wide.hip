@@ -20,11 +20,17 @@
 //     addend tile into that staging buffer first and the epilogue adds in fp32 before the one rounding; SP: the addend
 //     is the compact gradient of a strided subsample (conv1x1_addend.h) -- a lane's DMA offset is then computed from its
 //     pixel, and a pixel without an addend is fetched at the out-of-bounds offset (zeros, no traffic);
+//   * the inference use behind an eval-mode BatchNorm (conv1x1_wide_affine_kernel, AFF; no moments, no addend): the rounded
+//     values go through the BatchNorm's per-channel affine and ReLU (conv1x1_affine.h) in the accumulator layout, before
+//     the exchange.  There a register's channel depends on the lane half only and the wave's 32 channels are wave-uniform,
+//     so the 32 + 32 fp32 coefficients are scalar loads into SGPRs, selected per half -- the row-store lanes would need 16
+//     VGPRs for theirs, kept across the MFMAs of every block, which the K = 64 and K = 128 instances do not have to spare;
 //   * one barrier per pixel block; LDS traffic of the pipeline is inline asm with explicit waits (the compiler would put
 //     `s_waitcnt vmcnt(0)` in front of every LDS access it sees after an LDS-DMA load).
 #include <algorithm>
 
 #include "conv1x1_addend.h"
+#include "conv1x1_affine.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -73,11 +79,14 @@ template <int CPR>
 __device__ __forceinline__ int cw_swz(int row) { return CPR >= 16 ? (row & 15) : ((row >> 1) & 7); }
 __device__ __forceinline__ int cw_oswz(int row) { return row & 7; }
 
-template <typename T, int KS, bool MOM, bool ADD, bool SP>
+template <typename T, int KS, bool MOM, bool ADD, bool SP, bool AFF = false>
 __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const T* __restrict__ W, const T* __restrict__ A,
                                                   T* __restrict__ Y, float* __restrict__ part, int M, int N,
-                                                  int units_per_wg, int nsplits, int rows_total, AddendGeo ag) {
+                                                  int units_per_wg, int nsplits, int rows_total, AddendGeo ag,
+                                                  const float* __restrict__ sc = nullptr,
+                                                  const float* __restrict__ sh = nullptr, int relu = 0) {
   static_assert(ADD || !SP, "a compact addend is an addend");
+  static_assert(!(AFF && (MOM || ADD)), "the affine form is the plain forward of inference: no records, no addend");
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef Elem16<T> E;
   typedef typename E::x8 cw_x8;
@@ -92,7 +101,12 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
   const int per = gridDim.x >> 3;
   const int vid = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   if (vid >= groups * nsplits) return;
-  const int split = vid / groups, cg = vid - split * groups;
+  int split = vid / groups, cg = vid - split * groups;
+  if (AFF && KS > 4) {       // (uniform, but the division leaves them, and what derives from them, in vector registers, two more
+                             // than the K = 128 instance has; K = 64, held to 8 waves, is short of scalar registers instead)
+    split = __builtin_amdgcn_readfirstlane(split);
+    cg = __builtin_amdgcn_readfirstlane(cg);
+  }
   const int nblk = (M + 31) / 32;
   const int u_begin = split * units_per_wg;
   const int nun = min(units_per_wg, nblk - u_begin);            // >= 1 by construction of the grid
@@ -104,6 +118,13 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
     const u32x4* wp = reinterpret_cast<const u32x4*>(W + (size_t)(n0 + r) * K + h * 8);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) wf[ks] = __builtin_bit_cast(cw_x8, wp[ks * 2]);
+  }
+
+  // ---- AFF: the coefficients of this wave's 32 channels (uniform addresses: scalar registers) ----
+  float scw[AFF ? 32 : 1], shw[AFF ? 32 : 1];
+  if (AFF) {
+#pragma unroll
+    for (int i = 0; i < 32; ++i) { scw[i] = sc[n0 + i]; shw[i] = sh[n0 + i]; }
   }
 
   // ---- DMA plan ----
@@ -247,8 +268,32 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
         av[2 * i + 1] += E::hi(aw[i]);
       }
     }
+    // (AFF: nothing of the affine below may move up among the MFMAs, whose operands leave no register free at K = 64 and 128)
+    if (AFF) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) p[i] = E::pack(av[2 * i], av[2 * i + 1]);
+    if (AFF) {
+      // register e of lane half h holds channel (e & 3) + 8 * (e >> 2) + 4 * h: per half one of two scalars, selected by the
+      // constant lane mask of the upper half.  (The mask is made opaque per block: selects hoisted out of the loop would be
+      // 64 more vector registers, and a vector register for h is one more than the K = 64 and K = 128 instances have.)
+      unsigned long long upper = 0xffffffff00000000ull;
+      asm volatile("" : "+s"(upper));
+      auto half_of = [&](float lo, float hi) {
+        float o;
+        asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(o) : "v"(lo), "v"(hi), "s"(upper));
+        return o;
+      };
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        float yv[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int c = ((2 * i + j) & 3) + 8 * ((2 * i + j) >> 2);
+          yv[j] = affine1<T>(half_of(scw[c], scw[c + 4]), j ? E::hi(p[i]) : E::lo(p[i]), half_of(shw[c], shw[c + 4]), relu);
+        }
+        p[i] = E::pack(yv[0], yv[1]);
+      }
+    }
     if (MOM) {
       // (pair by pair: the sixteen decoded values need not be live together)
       if (u == 0) {              // (uniform) the pivots: this half-wave's pixel 0, which always exists
@@ -363,6 +408,30 @@ __global__ __launch_bounds__(kCwWaves* kWave) void conv1x1_wide_f16_kernel(const
   conv1x1_wide_body<f16_t, KS, MOM, ADD, SP>(X, W, A, Y, part, M, N, units_per_wg, nsplits, rows_total, ag);
 }
 
+// the forward in front of an eval-mode BatchNorm: y = T(relu?(sc * T(x w^T) + sh)) (names of their own, as above)
+// Held to the waves per SIMD the plain instances (no moments, no addend) they are launched in place of compile to.
+template <int KS> constexpr int kCwAffWaves = KS == 4 ? 8 : KS == 8 ? 5 : 2;
+template <int KS>
+__global__ __launch_bounds__(kCwWaves* kWave, kCwAffWaves<KS>) void conv1x1_wide_affine_kernel(const bf16_t* __restrict__ X,
+                                                                              const bf16_t* __restrict__ W,
+                                                                              const float* __restrict__ sc,
+                                                                              const float* __restrict__ sh, int relu,
+                                                                              bf16_t* __restrict__ Y, int M, int N,
+                                                                              int units_per_wg, int nsplits) {
+  conv1x1_wide_body<bf16_t, KS, false, false, false, true>(X, W, nullptr, Y, nullptr, M, N, units_per_wg, nsplits, 0,
+                                                           AddendGeo(), sc, sh, relu);
+}
+template <int KS>
+__global__ __launch_bounds__(kCwWaves* kWave, kCwAffWaves<KS>) void conv1x1_wide_f16_affine_kernel(const f16_t* __restrict__ X,
+                                                                                  const f16_t* __restrict__ W,
+                                                                                  const float* __restrict__ sc,
+                                                                                  const float* __restrict__ sh, int relu,
+                                                                                  f16_t* __restrict__ Y, int M, int N,
+                                                                                  int units_per_wg, int nsplits) {
+  conv1x1_wide_body<f16_t, KS, false, false, false, true>(X, W, nullptr, Y, nullptr, M, N, units_per_wg, nsplits, 0,
+                                                          AddendGeo(), sc, sh, relu);
+}
+
 struct CwPlan {
   int groups = 0, splits = 0, units_per_wg = 0, rows = 0;
 };
@@ -396,6 +465,25 @@ int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void
     if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
     hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD, SP>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
                        (const bf16_t*)a, (bf16_t*)y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
+  } else {
+    return MRLA_EUNSUPPORTED;
+  }
+  return hip_status(hipGetLastError());
+}
+
+template <int KS>
+int cw_launch_affine(const CwPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M,
+                     int N, int dtype, hipStream_t st) {
+  typedef CwGeo<KS, false> G;
+  const dim3 grid((p.groups * p.splits + 7) / 8 * 8), block(kCwWaves * kWave);
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_f16_affine_kernel<KS>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wide_f16_affine_kernel<KS>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w, sc, sh,
+                       relu, (f16_t*)y, M, N, p.units_per_wg, p.splits);
+  } else if (dtype == MRLA_BF16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_affine_kernel<KS>), G::kLds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wide_affine_kernel<KS>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, sc, sh,
+                       relu, (bf16_t*)y, M, N, p.units_per_wg, p.splits);
   } else {
     return MRLA_EUNSUPPORTED;
   }
@@ -452,6 +540,19 @@ int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend,
     case 64: return cw_launch<4, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
     case 128: return cw_launch<8, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
     case 256: return cw_launch<16, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
+    default: return MRLA_EUNSUPPORTED;
+  }
+}
+
+// y = T(relu?(sc * T(x w^T) + sh)): the plain forward's plan, grid and LDS, the affine applied before the tile is staged
+int launch_conv1x1_wide_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
+                               int N, int dtype, hipStream_t st) {
+  const CwPlan p = cw_plan(M, K, N);
+  if (!p.groups) return MRLA_EUNSUPPORTED;
+  switch (K) {
+    case 64: return cw_launch_affine<4>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
+    case 128: return cw_launch_affine<8>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
+    case 256: return cw_launch_affine<16>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
     default: return MRLA_EUNSUPPORTED;
   }
 }

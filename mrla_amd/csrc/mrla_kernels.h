@@ -177,6 +177,10 @@ int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M
 int conv1x1_addend_supported(int M, int K, int N);
 int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h, int wd,
                           int sh, int sw, int dtype, hipStream_t st);
+// ... + the eval-mode BatchNorm (+ReLU) behind it applied to the rounded product on its way out (inference; no records)
+int conv1x1_affine_supported(int M, int K, int N);
+int launch_conv1x1_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
+                          int N, int dtype, hipStream_t st);
 // stem_pool_nhwc.hip -- maxpool3x3/s2/p1(relu(bn(x))) without the intermediate tensor (channels_last, C % 64 == 0)
 int bn_pool_rows(int B, int C, int H, int W);
 int launch_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int B, int C, int H, int W,
@@ -192,6 +196,8 @@ int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* 
                         int dtype, hipStream_t st);
 int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
                                int wd, int sh, int sw, int dtype, hipStream_t st);      // compact addend of a strided subsample
+int launch_conv1x1_wide_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
+                               int N, int dtype, hipStream_t st);
 // conv1x1_kstream.hip -- the same product for wide reductions (K >= 512): both operands streamed through LDS; the tile copy-out takes the BatchNorm moment records as well
 int conv1x1_kstream_supported(int M, int K, int N);
 int conv1x1_kstream_stages(int M, int K, int N);      // LDS stages of the kernel the planner picks (3, or 4: the 256 x 256 tile)
@@ -199,6 +205,8 @@ int conv1x1_kstream_rows(int M, int K, int N);        // rows of the moment reco
 int launch_conv1x1_kstream(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st);
 int launch_conv1x1_kstream_addend(const void* x, const void* w, const void* addend, void* y, int M, int K, int N, int b, int h,
                                   int wd, int sh, int sw, int dtype, hipStream_t st);
+int launch_conv1x1_kstream_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M,
+                                  int K, int N, int dtype, hipStream_t st);
 // conv1x1_wgrad.hip -- its weight gradient dW[n,k] = sum_m dY[m,n] X[m,k] as a split-M MFMA GEMM (bf16 or fp16)
 int conv1x1_wgrad_rows(int M, int K, int N);
 int conv1x1_wgrad_plan(int M, int K, int N, int* out);

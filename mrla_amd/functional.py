@@ -77,6 +77,13 @@ CHANNEL_GATE = True   # a BatchNorm2d followed by channel attention (SE or ECA: 
 #                       norm layer or an active KernelTimer get either way).
 
 
+EVAL_FOLD = True  # a 1x1 GEMM convolution in front of an eval-mode BatchNorm2d (+ReLU), where nothing will be differentiated
+#                   (inference; the frozen first stage of the detection backbone), is ONE launch: the GEMM applies the
+#                   BatchNorm's fixed affine to its rounded product on the way out (mrla_conv1x1_fwd_affine) -- no apply pass,
+#                   no convolution-output-sized temporary.  False: the two launches, the same values bit for bit, kept for
+#                   A/B runs and tests.
+
+
 def _seq():
     return SEQUENCES and TIMER is None
 
@@ -1853,6 +1860,46 @@ def _conv_bn_fused(conv, bn, x, fused_bn):
     return lib.mrla_conv1x1_rows(m, k, n, dt) >= 0 and lib.mrla_conv1x1_wgrad_bn_supported(m, k, n, dt) == 1
 
 
+def _eval_fold_applies(conv, bn, x, fused_bn, defer):
+    """True when conv + bn on `x` (the GEMM's input) run as the one launch mrla_conv1x1_fwd_affine: the convolution on the
+    forward GEMM, a fused BatchNorm2d in eval mode behind it that is applied here (not deferred), and nothing to
+    differentiate -- the rule mrla_light uses for its inference form.  The fold has no backward."""
+    if not (EVAL_FOLD and fused_bn and not bn.training and not defer):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, conv.weight, bn.weight, bn.bias)):
+        return False
+    b, k, h, w = x.shape
+    lib, m, n, dt = L.load(), b * h * w, conv.out_channels, _DT[x.dtype]
+    return lib.mrla_conv1x1_rows(m, k, n, dt) >= 0 and lib.mrla_conv1x1_fwd_affine_supported(m, k, n, dt) == 1
+
+
+def _conv_bn_eval_fold(x, w, bn, relu):
+    """relu?(bn(conv1x1(x))) for an eval-mode BatchNorm2d in one GEMM launch (no autograd node: _eval_fold_applies).
+    x: channels_last [b, k, h, w]; w: the [n, k] (or [n, k, 1, 1]) weight in x's dtype."""
+    if x.device.index != torch.cuda.current_device():      # (launch where the buffers live: see _on_device)
+        with torch.cuda.device(x.device):
+            return _conv_bn_eval_fold(x, w, bn, relu)
+    b, k, h, wd = x.shape
+    n, m = w.shape[0], b * h * wd
+    dev, st, dt = x.device, _stream(), _DT[x.dtype]
+    w = w.detach().reshape(n, k)
+    if not w.is_contiguous():
+        w = w.contiguous()
+    gamma32, beta32 = _f32(bn.weight), _f32(bn.bias)
+    rs = _RunningStats(bn.running_mean, bn.running_var, n, "conv1x1 + eval-mode BatchNorm")
+    bnbuf = torch.empty((4, n), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
+    # (eval mode reads no sums, only the running statistics: one row of one pixel, in a buffer of its own -- the outputs are
+    # __restrict__)
+    amom = torch.empty((1, n, 2), dtype=torch.float32, device=dev)
+    _call("mrla_bn_stats_fwd", 0, _ptr(amom), None, _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv), L.BN_EVAL,
+          float(bn.momentum or 0.0), float(bn.eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), 1, n, 1, st)
+    y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
+    _call("mrla_conv1x1_fwd_affine", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w), _ptr(bnbuf[0]),
+          _ptr(bnbuf[1]), int(bool(relu)), _ptr(y), m, k, n, dt, st)
+    rs.finish(False)
+    return y
+
+
 def _strided_1x1(conv):
     """nn.Conv2d 1x1, no padding, stride > 1 (resnet_mrla_light.py:196-199: the downsample branch of a stage's first block)."""
     return (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1) and conv.stride != (1, 1)
@@ -1937,6 +1984,10 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
         if strided and not presampled:
             x = _SubsampleFn.apply(x, conv.stride[0], conv.stride[1])
         wt, w16, w16t = _gemm_weights(conv, x)
+        if _eval_fold_applies(conv, bn, x, fused_bn, defer):
+            # (`x` is the subsampled input of a strided downsample here; passthrough: as the route without a GEMM node below)
+            out = _conv_bn_eval_fold(x.detach(), w16 if w16 is not None else wt, bn, relu)
+            return (out, second(x)) if passthrough else out
         if _conv_bn_fused(conv, bn, x, fused_bn):
             training = bn.training
             momentum = bump_batch_counter(bn) if training else bn.momentum
