@@ -605,6 +605,19 @@ int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const 
                           void* dy_out, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                           void* stream);
 
+/* The same once more with the input-gradient GEMM behind it taken inside as well (two ADDITIVE symbols, MRLA_ABI_VERSION
+ * stays 5): dy is formed, multiplied into part / dw, and multiplied with the weight, dx[m, k] = dy[m, n] * w[n, k], for the
+ * workgroup's own pixels; dy itself is never written.  wt [k, n] is the weight's transposed 16-bit copy (what mrla_conv1x1_fwd
+ * takes as its weight for this product), dx [m, k] is written whole.  part and dw are bit-identical to mrla_conv1x1_wgrad_bn's,
+ * dx to mrla_conv1x1_fwd(dy_out, wt, dx, NULL, m, n, k, dtype) on the dy_out that call writes.  wt and dx must be 16-byte
+ * aligned and dx must be none of g, xb, x; the other conditions are mrla_conv1x1_wgrad_bn's.
+ * mrla_conv1x1_wgrad_bn_dx_supported: 1 where mrla_conv1x1_wgrad_bn_supported is 1 and ONE 256 x 64 tile covers all of n and
+ * k (n = 256, k = 64: the workgroup then holds whole rows of dy); else MRLA_EUNSUPPORTED, from both. */
+int mrla_conv1x1_wgrad_bn_dx_supported(int m, int k, int n, int dtype);
+int mrla_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb /*[n,3]*/,
+                             int relu, const void* x, const void* wt /*[k,n]*/, void* dx /*[m,k]*/, float* part, void* dw,
+                             int m, int k, int n, int dtype, int dw_dtype, void* stream);
+
 /* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input
  * gradient): replaces what torch.autocast does in front of nn.Conv2d (resnet/train.py runs fp32; the bf16 configuration of

@@ -105,6 +105,8 @@ SIGNATURES = {
     "mrla_conv1x1_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_supported": [_I] * 4,
     "mrla_conv1x1_wgrad_bn": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "mrla_conv1x1_wgrad_bn_dx_supported": [_I] * 4,
+    "mrla_conv1x1_wgrad_bn_dx": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],
     "mrla_weight_bank_refresh_dt": [_P, _I, _I, _I, _P],
     "mrla_reduce_rows": [_P, _P, _I, _I, _P],

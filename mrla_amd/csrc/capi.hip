@@ -771,6 +771,27 @@ int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const 
                                  (hipStream_t)stream);
 }
 
+int mrla_conv1x1_wgrad_bn_dx_supported(int m, int k, int n, int dtype) {
+  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return conv1x1_wgrad_bn_dx_supported(m, k, n);
+}
+
+int mrla_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                             const void* x, const void* wt, void* dx, float* part, void* dw, int m, int k, int n, int dtype,
+                             int dw_dtype, void* stream) {
+  if (!g || !xb || !sc || !sh || !cb || !x || !wt || !dx || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype))
+    return MRLA_EINVAL;
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  // as mrla_conv1x1_wgrad_bn; a lane reads 16 bytes of a row of wt and stores 16 bytes of a row of dx
+  if (((uintptr_t)sc | (uintptr_t)sh | (uintptr_t)cb | (uintptr_t)wt | (uintptr_t)dx) & 15) return MRLA_EINVAL;
+  if (dx == g || dx == xb || dx == x) return MRLA_EINVAL;      // dx is written while g, xb and x are still read
+  return launch_conv1x1_wgrad_bn_dx(g, xb, sc, sh, cb, relu, x, wt, dx, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype,
+                                    (hipStream_t)stream);
+}
+
 int mrla_weight_bank_refresh(const void* table, int entries, int max_tiles, void* stream) {
   if (!table || entries <= 0 || max_tiles <= 0) return MRLA_EINVAL;
   return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, MRLA_BF16, (hipStream_t)stream);

@@ -34,6 +34,15 @@
 // 16 bytes to dy_out for the input-gradient GEMM (k-tile 0 only: the others get the store offset of a killed chunk, so
 // the number of stores in flight, which the counted waits include, is one constant).  The MFMAs then see exactly the
 // bytes mrla_bn_act_bwd would have written: bit-identical partial tiles.
+//
+// The BN + dX form (mrla_conv1x1_wgrad_bn_dx) takes the input-gradient GEMM behind this one into it as well, where ONE
+// 256 x 64 tile covers all of N and K (stage 1's conv3 and downsample): dX[m, k] = dy[m, n] W[n, k] for the workgroup's own
+// pixel chunks, and no dy_out -- dy, four times the size of X and dX there, never leaves the CU.  The published g tile of a
+// stage IS the rounded dy[32 px][256]; two of the four waves (0/1 on even chunks, 2/3 on odd ones) multiply it with their 32
+// rows of W^T, which they hold in registers for the whole kernel, with the narrow GEMM's instruction, operand roles and ONE
+// accumulation chain in ascending k (conv1x1.hip, conv1x1_fwd_body): bit-identical to that launch on dy_out.  The rounded
+// pieces are staged in the stage's xb tile (dead once the stage has been rewritten), and behind the chunk's barrier -- the
+// pipeline's own -- all four waves store the 32 whole 128-byte lines, one counted store per wave and chunk.
 #include <algorithm>
 #include <type_traits>
 
@@ -118,6 +127,13 @@ struct WgBnArgs {
   int relu;
 };
 
+// what the BN + dX form reads and writes beside those (it stores no dy_out)
+struct WgDxArgs {
+  const void* wt;                 // [K, N] the weight's transposed working copy
+  void* dx;                       // [M, K]
+};
+constexpr int kDxRowB = 64 * 2 + 16;      // padded row of the dX staging tile (64 channels of one pixel), as conv1x1.hip's
+
 __device__ __forceinline__ void wg_read16(u32x4& v, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
 }
@@ -135,15 +151,17 @@ __device__ __forceinline__ void wg_fence16(u32x4& v, bool wait) {
 
 // grid: tiles * splits workgroups (tiles = (N/TN)*(K/TK)) padded to a multiple of 8; 256 threads; LDS = ST * SB
 // BN: dY is g, and a stage is SB + YB bytes (the xb tile behind the two operand tiles)
-template <typename T, int TN, int TK, int ST, int PC, bool BN>
+// DX (BN, one tile over all of N = 256 and K = 64): dX = dy W as well, no dy_out; grid and LDS as the BN form's
+template <typename T, int TN, int TK, int ST, int PC, bool BN, bool DX = false>
 __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, const T* __restrict__ X,
                                                    float* __restrict__ part, int M, int N, int K, int chunks_per_wg,
-                                                   int nsplits, const WgBnArgs& bn) {
+                                                   int nsplits, const WgBnArgs& bn, const WgDxArgs& dxa = WgDxArgs{}) {
 #if defined(__HIP_DEVICE_COMPILE__)
   typedef WgGeo<TN, TK, PC> G;
   constexpr int CPRY = TN / 8, CPRX = TK / 8;            // 16-byte chunks per tile row
   constexpr int SB = G::SB + (BN ? G::YB : 0);           // bytes of one stage
   static_assert(G::SB < 65536, "ds offset field");
+  static_assert(!DX || (BN && TN == 256 && TK == 64 && PC == 32), "the dX form: one 256 x 64 tile");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -248,6 +266,21 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 #pragma unroll
     for (int q = 0; q < 8; ++q) asm volatile("" : "+v"(scv[q]), "+v"(shv[q]));
   }
+  // ---- DX: this wave's 32 rows of W^T as MFMA A fragments (all 16 k-steps: 64 registers), the store lane's first offset ----
+  // Waves 0/1 take the two 32-channel output blocks of the even chunks, waves 2/3 those of the odd ones.
+  u32x4 wa[DX ? 16 : 1];
+  const auto rsD = __builtin_amdgcn_make_buffer_rsrc(DX ? dxa.dx : nullptr, 0, DX ? (int)((size_t)M * K * 2) : 0, MRLA_WG_FLAGS);
+  const unsigned dlimit = (unsigned)((size_t)M * K * 2);
+  const int dr = lane & 31, dh = lane >> 5, dblk = wave & 1;
+  unsigned doff = 0;                                     // this lane's 16 bytes of the dX lines of the chunk stored next
+  if constexpr (DX) {
+    const u32x4* wp = reinterpret_cast<const u32x4*>(static_cast<const T*>(dxa.wt) + (size_t)(dblk * 32 + dr) * N + dh * 8);
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) wa[ks] = wp[ks * 2];
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) asm volatile("" : "+v"(wa[ks]));      // (pinned in front of the first DMA, as the coefficients)
+    doff = (unsigned)(((size_t)c_begin * PC + wave * 8 + (lane >> 3)) * K * 2 + (lane & 7) * 16);
+  }
   const int relu = BN ? bn.relu : 0;
   // the pieces this lane's DMA instructions dropped into the stage at byte offset sbo: g -> dy in place and to dy_out.
   // Call it behind the counted vmcnt that covers the stage and in front of the barrier that publishes it.
@@ -285,10 +318,58 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
         o[w] = live ? Elem16<T>::pack(y[0], y[1]) : 0u;
       }
       wg_write16(at + i * (kWgWaves * 1024), o);
-      __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (live ? off : 0x80000000u) | skill, 0, 0);
+      if constexpr (!DX) __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (live ? off : 0x80000000u) | skill, 0, 0);
     }
     toff += advY;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+
+  // DX: dX[32 px][32 ch] of the published stage at sbo, the narrow GEMM's arithmetic (conv1x1_fwd_body with KS = 16): A = 32
+  // rows of W^T, B = the lane's pixel's 16 bytes of dy per k-step -- a plain read of the rewritten g tile -- ONE chain of 16
+  // MFMAs in ascending k, rounding, the half-wave exchange.  The two 16-byte pieces go to the stage's xb tile, which is dead
+  // once the stage has been rewritten, as rows of kDxRowB bytes.  Waits for every LDS read of the wave outstanding.
+  auto dx_chunk = [&](unsigned sbo) {
+    u32x4 bq[16];
+    const unsigned rowa = lds0 + sbo + dr * (CPRY * 16);
+    const int sw = swz<CPRY>(dr);
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) wg_read16(bq[ks], rowa + (((2 * ks + dh) ^ sw) << 4));
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks) wg_fence16(bq[ks], ks == 0);
+    wg_f32x16 d;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) d[e] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 16; ++ks)
+      Elem16<T>::mfma(d, __builtin_bit_cast(typename Elem16<T>::x8, wa[ks]), __builtin_bit_cast(typename Elem16<T>::x8, bq[ks]));
+    unsigned p[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = Elem16<T>::pack(d[2 * i], d[2 * i + 1]);
+    // half 0 holds channels {0-3, 8-11, 16-19, 24-27} of its pixel, half 1 the others; after the swaps half 0 holds
+    // {0-7, 16-23} and half 1 {8-15, 24-31}
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const auto sx = __builtin_amdgcn_permlane32_swap(p[4 * g + q], p[4 * g + 2 + q], false, false);
+        p[4 * g + q] = sx[0];
+        p[4 * g + 2 + q] = sx[1];
+      }
+    }
+    const unsigned to = lds0 + sbo + G::SB + dr * kDxRowB + (dblk * 32 + dh * 8) * 2;
+    wg_write16(to, (u32x4){p[0], p[1], p[2], p[3]});
+    wg_write16(to + 32, (u32x4){p[4], p[5], p[6], p[7]});
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  };
+  // DX: the 32 lines (128 bytes) of the chunk staged at sbo, one 16-byte piece per lane of the workgroup; behind the
+  // barrier that follows the chunk's dx_chunk.  ONE store per wave and chunk whatever M is (a row at or past M: the
+  // out-of-range offset), so that the counted waits stay constants.
+  auto dx_store = [&](unsigned sbo) {
+    u32x4 v;
+    wg_read16(v, lds0 + sbo + G::SB + (wave * 8 + (lane >> 3)) * kDxRowB + (lane & 7) * 16);
+    wg_fence16(v, true);
+    __builtin_amdgcn_raw_buffer_store_b128(v, rsD, doff < dlimit ? doff : 0x80000000u, 0, 0);
+    doff += advX;
   };
 
   // ST stages rotate.  Chunks past the range are issued all the same, with an out-of-bounds offset (zeros from the
@@ -303,7 +384,13 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   // so when iteration c waits for I(c+1) there are ST-3 later I behind it, and S: ST-3 of them in the steady state,
   // only S(0) in iteration 0 (none at all with three stages).  A smaller count only waits for more, so the constant
   // is the least of these.
-  constexpr int W_NEXT = (ST - 3) * NI + (BN && ST > 3 ? G::NIY : 0);
+  // DX: no S; the one store D(c) of chunk c's dX lines follows the barrier of iteration c, in front of I(c+ST-1), and a
+  // killed store D(-1) follows the prologue's barrier:
+  //   I(0) .. I(ST-2) D(-1) | D(0) I(ST-1) | D(1) I(ST) | ...
+  // so behind I(c+1) there are, in every iteration, ST-3 later I and ST-3 D (iteration 0: I(2) and D(-1); iteration c:
+  // D(c-1) and I(c+2)).  The prologue waits for I(0) in front of D(-1): its count is the BN form's.
+  constexpr int W_NEXT = (ST - 3) * NI + (DX ? ST - 3 : BN && ST > 3 ? G::NIY : 0);
+  static_assert(!DX || ST == 4, "the dX form's store stream is counted for four stages");
   static_assert(KSN % 2 == 0 && ST >= 3 && W_NEXT < 64 && (ST - 2) * NI < 64, "fragment double buffer / stages / vmcnt immediate");
   Frag fa[2][G::BN], fb[2][G::BK];
   auto read_step = [&](int buf, unsigned sbo, int ks) {
@@ -325,6 +412,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   if constexpr (BN) rewrite(0);
   __builtin_amdgcn_s_barrier();                         // (bare: __syncthreads() would drain vmcnt as well)
   asm volatile("" ::: "memory");
+  if constexpr (DX) __builtin_amdgcn_raw_buffer_store_b128((u32x4){0u, 0u, 0u, 0u}, rsD, 0x80000000u, 0, 0);      // D(-1)
   read_step(0, 0, 0);
   int stage = 0, nxt = ST - 1;
   for (int c = 0; c < nch; ++c) {
@@ -341,6 +429,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
         if constexpr (BN) rewrite(stage * SB);
         __builtin_amdgcn_s_barrier();                   // everybody's has; everybody is done reading chunk c-1
         asm volatile("" ::: "memory");
+        if constexpr (DX) dx_store(sbo);                // chunk c's dX lines: both of its waves staged them in front of the barrier
         issue(nxt);
         nxt = nxt + 1 == ST ? 0 : nxt + 1;
         read_step(0, stage * SB, 0);
@@ -354,7 +443,15 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 #pragma unroll
       for (int j = 0; j < G::BK; ++j) frag_fence<0>(fb[cur][j], false);
       mfma_step(cur);
+      if constexpr (DX) {
+        if (ks == 0 && (c & 1) == (wave >> 1)) dx_chunk(sbo);      // (behind MFMAs already queued; wave-uniform)
+      }
     }
+  }
+  if constexpr (DX) {              // the last chunk's lines: no hand-over published them
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    dx_store((stage == 0 ? ST - 1 : stage - 1) * SB);
   }
 
   // ---- partial tile: D[i][j], j = lane % 32 on the lane, i = 8*(e/4) + 4*(lane/32) + e%4 in register e ----
@@ -400,6 +497,24 @@ __global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_bn_f16_kernel(c
                                                                                int K, int chunks_per_wg, int nsplits,
                                                                                WgBnArgs bn) {
   conv1x1_wgrad_body<f16_t, TN, TK, ST, PC, true>(g, X, part, M, N, K, chunks_per_wg, nsplits, bn);
+}
+
+// the BN + dX form (256 x 64 only), both types: names of their own, the BN instances above are not touched
+template <int ST>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_bn_dx_kernel(const bf16_t* __restrict__ g,
+                                                                              const bf16_t* __restrict__ X,
+                                                                              float* __restrict__ part, int M, int N, int K,
+                                                                              int chunks_per_wg, int nsplits, WgBnArgs bn,
+                                                                              WgDxArgs dxa) {
+  conv1x1_wgrad_body<bf16_t, 256, 64, ST, kPC, true, true>(g, X, part, M, N, K, chunks_per_wg, nsplits, bn, dxa);
+}
+template <int ST>
+__global__ __launch_bounds__(kWgWaves* kWave) void conv1x1_wgrad_bn_dx_f16_kernel(const f16_t* __restrict__ g,
+                                                                                  const f16_t* __restrict__ X,
+                                                                                  float* __restrict__ part, int M, int N,
+                                                                                  int K, int chunks_per_wg, int nsplits,
+                                                                                  WgBnArgs bn, WgDxArgs dxa) {
+  conv1x1_wgrad_body<f16_t, 256, 64, ST, kPC, true, true>(g, X, part, M, N, K, chunks_per_wg, nsplits, bn, dxa);
 }
 
 // dW[e] = sum over splits of part[s][e] in a fixed order: a workgroup takes 64 outputs, its 16 groups of 16 lanes take
@@ -500,6 +615,25 @@ int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int
   return MRLA_OK;
 }
 
+// the BN + dX form: the BN form's grid and LDS (the dX staging lives in the xb tiles)
+int launch_tile_dx(const WgPlan& p, const void* g, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st,
+                   const WgBnArgs& bn, const WgDxArgs& dxa) {
+  typedef WgGeo<256, 64, kPC> G;
+  const dim3 grid((p.tiles * p.splits + 7) / 8 * 8), block(kWgWaves * kWave);
+  constexpr size_t lds = (size_t)kWgStages * (G::SB + G::YB);
+  static_assert(lds <= 160 * 1024 && kPC * kDxRowB <= G::YB, "LDS of a CU / the staging tile inside the xb tile");
+  if (dtype == MRLA_F16) {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_dx_f16_kernel<kWgStages>), lds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wgrad_bn_dx_f16_kernel<kWgStages>), grid, block, lds, st, (const f16_t*)g, (const f16_t*)x, part, M,
+                       N, K, p.chunks_per_wg, p.splits, bn, dxa);
+  } else {
+    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_dx_kernel<kWgStages>), lds) != hipSuccess) return MRLA_EHIP;
+    hipLaunchKernelGGL((conv1x1_wgrad_bn_dx_kernel<kWgStages>), grid, block, lds, st, (const bf16_t*)g, (const bf16_t*)x, part, M,
+                       N, K, p.chunks_per_wg, p.splits, bn, dxa);
+  }
+  return MRLA_OK;
+}
+
 }  // namespace
 
 int conv1x1_wgrad_rows(int M, int K, int N) {
@@ -527,17 +661,30 @@ int conv1x1_wgrad_bn_supported(int M, int K, int N) {
   return ktiles == 1 || (ktiles == 2 && N <= 512) ? 1 : MRLA_EUNSUPPORTED;
 }
 
-// bn [opt]: the BN form -- dy is then g, the gradient at the BatchNorm's output
+// The shapes the BN + dX form takes: the BN form's whose one 256 x 64 tile covers all of N and K, so that the workgroup holds
+// whole rows of dy (the reduction of dX) and writes whole rows of dX.
+int conv1x1_wgrad_bn_dx_supported(int M, int K, int N) {
+  if (conv1x1_wgrad_bn_supported(M, K, N) != 1) return MRLA_EUNSUPPORTED;
+  const WgPlan p = wgrad_plan(M, K, N);
+  return p.tiles == 1 && p.tn == 256 && p.tk == 64 ? 1 : MRLA_EUNSUPPORTED;
+}
+
+// bn [opt]: the BN form -- dy is then g, the gradient at the BatchNorm's output; dxa [opt, with bn]: the BN + dX form
 static int launch_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
-                        hipStream_t st, const WgBnArgs* bn) {
+                        hipStream_t st, const WgBnArgs* bn, const WgDxArgs* dxa = nullptr) {
   const WgPlan p = wgrad_plan(M, K, N);
   if (!p.tiles || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
   int rc = MRLA_EUNSUPPORTED;
+  if (dxa) {
+    if (!bn || conv1x1_wgrad_bn_dx_supported(M, K, N) != 1) return MRLA_EUNSUPPORTED;
+    rc = launch_tile_dx(p, dy, x, part, M, K, N, dtype, st, *bn, *dxa);
+  } else {
 #define MRLA_WG_TILE(A, B) \
   if (p.tn == A && p.tk == B) rc = launch_tile<A, B, kWgStages, kPC>(p, dy, x, part, M, K, N, dtype, st, bn);
-  MRLA_WG_TILE(64, 64) MRLA_WG_TILE(64, 128) MRLA_WG_TILE(64, 256) MRLA_WG_TILE(128, 64) MRLA_WG_TILE(128, 128)
-  MRLA_WG_TILE(128, 256) MRLA_WG_TILE(256, 64) MRLA_WG_TILE(256, 128)
+    MRLA_WG_TILE(64, 64) MRLA_WG_TILE(64, 128) MRLA_WG_TILE(64, 256) MRLA_WG_TILE(128, 64) MRLA_WG_TILE(128, 128)
+    MRLA_WG_TILE(128, 256) MRLA_WG_TILE(256, 64) MRLA_WG_TILE(256, 128)
 #undef MRLA_WG_TILE
+  }
   if (rc != MRLA_OK) return rc;
   const int NK = N * K;
   if (dw_f32)      // the fp32 master weight's gradient directly (no cast kernel behind an autocast convolution)
@@ -560,6 +707,15 @@ int launch_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, cons
   if (conv1x1_wgrad_bn_supported(M, K, N) != 1) return MRLA_EUNSUPPORTED;
   const WgBnArgs bn{xb, cb, sc, sh, dy_out, relu};
   return launch_wgrad(g, x, part, dw, dw_f32, M, K, N, dtype, st, &bn);
+}
+
+int launch_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                               const void* x, const void* wt, void* dx, float* part, void* dw, int dw_f32, int M, int K, int N,
+                               int dtype, hipStream_t st) {
+  if (conv1x1_wgrad_bn_dx_supported(M, K, N) != 1) return MRLA_EUNSUPPORTED;
+  const WgBnArgs bn{xb, cb, sc, sh, nullptr, relu};
+  const WgDxArgs dxa{wt, dx};
+  return launch_wgrad(g, x, part, dw, dw_f32, M, K, N, dtype, st, &bn, &dxa);
 }
 
 }  // namespace mrla

@@ -217,6 +217,11 @@ int conv1x1_wgrad_bn_supported(int M, int K, int N);
 int launch_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
                             void* dy_out, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
                             hipStream_t st);
+// ... and with dx = dy w formed inside it as well (one 256 x 64 tile: n = 256, k = 64); no dy_out
+int conv1x1_wgrad_bn_dx_supported(int M, int K, int N);
+int launch_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
+                               const void* x, const void* wt, void* dx, float* part, void* dw, int dw_f32, int M, int K, int N,
+                               int dtype, hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)

@@ -70,6 +70,14 @@ WGRAD_BN = True   # a 1x1 GEMM convolution + BatchNorm2d pair is one autograd no
 #                   False: the two nodes and the per-pass route -- the same values bit for bit, kept for A/B runs and tests.
 
 
+WGRAD_BN_DX = True   # where the call site asks for it (conv_bn_act(..., fuse_dx=True): the bottleneck's conv3 and downsample) and
+#                      one workgroup tile of that GEMM covers all channels of both sides (n = 256, k = 64: stage 1), it forms the convolution's input gradient dx = dy w as well (mrla_conv1x1_wgrad_bn_dx):
+#                      dy, the largest tensor of the block, is neither written nor read back, and the input-gradient GEMM's
+#                      launch is gone.  False: mrla_conv1x1_wgrad_bn and the input-gradient GEMM -- the same values bit for bit,
+#                      kept for A/B runs and tests (and what a frozen input, a shortcut gradient arriving or any other shape
+#                      get either way).
+
+
 CHANNEL_GATE = True   # a BatchNorm2d followed by channel attention (SE or ECA: resnet_mrla_light.py:77-81,105-108) is one autograd
 #                       node on the HIP passes of bn_gate_nhwc.hip: 3 passes over the activation forward and 5 backward, the
 #                       BatchNorm's output never stored (bn_gate).  False: bn_act, then the eager se_layer / eca_layer modules --
@@ -1759,8 +1767,9 @@ class _ConvBnFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def forward(ctx, x, w, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer, box, passthrough,
-                w16, w16t, sub):
+                w16, w16t, sub, fuse_dx=False):
         ctx.set_materialize_grads(False)
+        ctx.fuse_dx = bool(fuse_dx)
         ca, cb = _SubCtx(), _SubCtx()
         # (gradients are off inside a forward: this call adds no node, it is _Conv1x1Fn's forward and nothing else.  Through
         # .apply, not .forward(ca, ...): _Conv1x1Fn.apply is where the GEMM route is observed from outside, for this node too;
@@ -1802,7 +1811,7 @@ class _ConvBnFn(torch.autograd.Function):
         ca.needs_input_grad = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         x, w, _ = saved[:3]
         y, gamma32, bnbuf = saved[3:]
-        tail = (None,) * 12
+        tail = (None,) * 13
         if dy is None:             # only the shortcut carried a gradient
             gx = _Conv1x1Fn.backward(ca, None, None, d_through)[0]
             return (gx, None, None, None) + tail
@@ -1839,6 +1848,16 @@ class _ConvBnFn(torch.autograd.Function):
         prow = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
         part = torch.empty((prow, n, k), dtype=torch.float32, device=dev)
         gw = torch.empty((n, k), dtype=ca.wdtype, device=dev)
+        if (WGRAD_BN_DX and ctx.fuse_dx and ctx.needs_input_grad[0] and d_through is None and ca.sub is None
+                and lib.mrla_conv1x1_wgrad_bn_dx_supported(m, k, n, dt) == 1):
+            # dx = dy w inside the same launch: dy never leaves the kernel (wt as _Conv1x1Fn.backward takes it)
+            w16t = saved[2]
+            wt = w16t if w16t is not None else w.t().contiguous()
+            gx = torch.empty_like(x)
+            L.call("mrla_conv1x1_wgrad_bn_dx", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(small), cb.relu, _ptr(x),
+                   _ptr(wt), _ptr(gx), _ptr(part), _ptr(gw), m, k, n, dt, _DT[ca.wdtype], st)
+            gw = _grad_like(gw, ca.wshape, ca.wstride)
+            return (gx, gw, small[3].to(cb.gdtype), small[4].to(cb.gdtype)) + tail
         dyc = torch.empty_like(y)
         L.call("mrla_conv1x1_wgrad_bn", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(small), cb.relu, _ptr(dyc),
                _ptr(x), _ptr(part), _ptr(gw), m, k, n, dt, _DT[ca.wdtype], st)
@@ -1958,7 +1977,7 @@ def _gemm_weights(conv, x):
     return wt, w16, w16t
 
 
-def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=None, presampled=False):
+def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=None, presampled=False, fuse_dx=False):
     """relu?(bn(conv(x))) -- resnet_mrla_light.py:93-94,100-101.  Eligible 1x1 convolutions run on the HIP GEMM, whose
     epilogue hands the train-mode BatchNorm its statistics (the moments pass over the output disappears); everything
     else is `bn_act(conv(x), ...)` with the stock convolution.
@@ -1968,7 +1987,10 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
     subsample=(sh, sw), with passthrough: x' is x[:, :, ::sh, ::sw] routed the same way -- the input of the block's strided
     downsample convolution (shortcut_subsample), whose input gradient then reaches the GEMM compact instead of scattered
     into a zero-filled tensor of x's size.  presampled=True: `conv` is that strided 1x1 convolution and `x` the already
-    subsampled input."""
+    subsampled input.
+    fuse_dx=True: where the pair runs as the one node _ConvBnFn and the shape allows it, the backward forms the input gradient
+    inside the weight-gradient launch as well (WGRAD_BN_DX, mrla_conv1x1_wgrad_bn_dx) -- the same values bit for bit; the
+    bottleneck asks for it on conv3 and the downsample.  Without it the backward launches what it always launched."""
     def second(t):                  # the second result where the convolution's own node does not produce it
         return _SubsampleFn.apply(t, subsample[0], subsample[1]) if subsample is not None else t
 
@@ -1994,7 +2016,7 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
             box = _DeferredBnBox() if defer else None
             through = passthrough and x.requires_grad
             res = _ConvBnFn.apply(x, wt, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0,
-                                  bn.eps, relu, defer, box, through, w16, w16t, subsample if through else None)
+                                  bn.eps, relu, defer, box, through, w16, w16t, subsample if through else None, fuse_dx)
             res = res if isinstance(res, tuple) else (res,)
             out = res[0]
             if defer:

@@ -100,11 +100,11 @@ class _BottleneckTrunk(nn.Module):
                 cl = out.is_contiguous(memory_format=torch.channels_last) and not out.is_contiguous()
                 defer_bn3 = defer_bn3(torch.empty((b_, self.conv3.out_channels, h_, w_), dtype=out.dtype, device="meta",
                                                   memory_format=torch.channels_last if cl else torch.contiguous_format))
-            out = F_.conv_bn_act(out, self.conv3, self.bn3, relu=False, defer=defer_bn3)
+            out = F_.conv_bn_act(out, self.conv3, self.bn3, relu=False, defer=defer_bn3, fuse_dx=True)
         if self.downsample is not None:
             ds = self.downsample
             if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d):
-                identity = F_.conv_bn_act(identity, ds[0], ds[1], relu=False, presampled=sub is not None)
+                identity = F_.conv_bn_act(identity, ds[0], ds[1], relu=False, presampled=sub is not None, fuse_dx=True)
             else:
                 identity = ds(identity)
         return out, identity
