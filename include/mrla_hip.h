@@ -77,7 +77,7 @@ enum { MRLA_BN_NONE = 0, MRLA_BN_TRAIN = 1, MRLA_BN_EVAL = 2 };
  *           ranges too, nothing else changes for a caller.  mrla_tuning_row_ranges() was added.
  *           Additive since (no bump): every mrla_conv1x1_* entry point takes MRLA_F16 wherever it takes MRLA_BF16, with the
  *           same answers for the same (m, k, n) -- callers that pass MRLA_BF16 see no change -- and
- *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh.
+ *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh;  mrla_bn_pool_plan was added.
  * A consumer compares mrla_abi_version() (what the loaded library was built from) against this constant before its
  * first call. */
 #define MRLA_ABI_VERSION 5
@@ -448,6 +448,11 @@ int mrla_bn_act_bwd(const void* dy, const void* x, const float* sc, const float*
  *             maximum is > 0;  tmom[rows,c,2] = (sum dz, sum dz*x) with rows = mrla_bn_pool_rows();  dx = e*dz + f*x + h.
  * mrla_bn_pool_rows returns MRLA_EUNSUPPORTED for MRLA_NCHW or c % 64 != 0: the caller keeps bn_act + its own pooling. */
 int mrla_bn_pool_rows(int b, int c, int h, int w, int dtype, int layout);
+/* Host-side query of the geometry the three passes run with (additive, no ABI bump): out[6] = Ho, Wo, row bands per image
+ * (mrla_bn_pool_rows() = b * bands; tmom row = image * bands + band), waves per workgroup, and the window rows [ho0, ho1) of
+ * `band` -- the bands tile [0, Ho) in order and none is empty.  MRLA_EINVAL for band outside [0, bands) or out == NULL;
+ * otherwise the refusals of mrla_bn_pool_rows. */
+int mrla_bn_pool_plan(int b, int c, int h, int w, int dtype, int layout, int band, int* out);
 int mrla_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int b, int c, int h, int w, int dtype,
                           int layout, void* stream);
 int mrla_bn_relu_pool_dmoments(const void* dp, const void* x, const float* sc, const float* sh, const float* center /*[opt]*/,

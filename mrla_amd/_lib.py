@@ -81,6 +81,7 @@ SIGNATURES = {
     "mrla_bn_plane_dmoments": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_act_bwd": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_pool_rows": [_I] * 6,
+    "mrla_bn_pool_plan": [_I] * 7 + [_P],
     "mrla_bn_relu_pool_fwd": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_relu_pool_dmoments": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "mrla_bn_relu_pool_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -174,6 +175,13 @@ def conv1x1_wgrad_plan(m, k, n, dtype=None):
     """(chunks per workgroup, LDS stages, tile n, tile k, splits, tiles) of mrla_conv1x1_wgrad, or None."""
     out = (ctypes.c_int * 6)()
     rc = load().mrla_conv1x1_wgrad_plan(m, k, n, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
+def bn_pool_plan(b, c, h, w, dtype, band=0):
+    """(Ho, Wo, row bands per image, waves per workgroup, ho0, ho1 of `band`) of the mrla_bn_relu_pool_* passes, or None."""
+    out = (ctypes.c_int * 6)()
+    rc = load().mrla_bn_pool_plan(b, c, h, w, dtype, NHWC, band, ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 

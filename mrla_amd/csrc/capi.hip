@@ -642,6 +642,12 @@ int mrla_bn_pool_rows(int b, int c, int h, int w, int dtype, int layout) {
   return bn_pool_rows(b, c, h, w);
 }
 
+int mrla_bn_pool_plan(int b, int c, int h, int w, int dtype, int layout, int band, int* out) {
+  if (bad_dims(b, c, h, w) || bad_dtype(dtype) || !out) return MRLA_EINVAL;
+  if (layout != MRLA_NHWC) return layout == MRLA_NCHW ? MRLA_EUNSUPPORTED : MRLA_EINVAL;
+  return bn_pool_plan(b, c, h, w, band, out);
+}
+
 int mrla_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int b, int c, int h, int w, int dtype,
                           int layout, void* stream) {
   if (!x || !sc || !sh || !out || bad_dims(b, c, h, w) || bad_dtype(dtype)) return MRLA_EINVAL;

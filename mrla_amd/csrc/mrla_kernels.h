@@ -183,6 +183,7 @@ int launch_conv1x1_affine(const void* x, const void* w, const float* sc, const f
                           int N, int dtype, hipStream_t st);
 // stem_pool_nhwc.hip -- maxpool3x3/s2/p1(relu(bn(x))) without the intermediate tensor (channels_last, C % 64 == 0)
 int bn_pool_rows(int B, int C, int H, int W);
+int bn_pool_plan(int B, int C, int H, int W, int band, int* out);
 int launch_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int B, int C, int H, int W,
                             int dtype, hipStream_t st);
 int launch_bn_relu_pool_dmoments(const void* dp, const void* x, const float* sc, const float* sh, const float* center,

@@ -36,6 +36,17 @@ __device__ __forceinline__ void activate(const RawRow<NPX>& x, float (&a)[NPX], 
   }
 }
 
+// Window rows [ho0, ho1) of row band `band`: the balanced split [band * Ho / bands, (band + 1) * Ho / bands).  pool_geo keeps
+// Ho >= 4 * bands, so no band is empty (the backward kernel always runs a band's last steps: an empty one would store rows
+// that are not its own), and where bands divides Ho every band has Ho / bands rows.  bands is a power of two <= 32 (pool_geo):
+// a shift, not a division, and 32 * Ho fits 32 bits.  The one place that knows the partition: the kernels' prologue and
+// mrla_bn_pool_plan both ask here.
+__host__ __device__ __forceinline__ void pool_band_rows(int Ho, int bands, int band, int& ho0, int& ho1) {
+  const int shift = __builtin_ctz((unsigned)bands);
+  ho0 = (int)(((unsigned)band * (unsigned)Ho) >> shift);
+  ho1 = (int)(((unsigned)(band + 1) * (unsigned)Ho) >> shift);
+}
+
 #define MRLA_POOL_PROLOGUE(NRED, WAVE_BYTES)                                                             \
   extern __shared__ __align__(16) unsigned char smem_raw[];                                              \
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;   \
@@ -43,8 +54,8 @@ __device__ __forceinline__ void activate(const RawRow<NPX>& x, float (&a)[NPX], 
   unsigned char* wbuf = smem_raw + (size_t)nwaves * (NRED) * kWave * sizeof(float) + (size_t)wave * (WAVE_BYTES); \
   const int cbase = blockIdx.x * kWave, c = cbase + lane;                                                \
   const int b = blockIdx.y / bands, band = blockIdx.y - b * bands;                                       \
-  const int rows_per = (Ho + bands - 1) / bands;                                                         \
-  const int ho0 = band * rows_per, ho1 = min(Ho, ho0 + rows_per);                                        \
+  int ho0, ho1;                                                                                          \
+  pool_band_rows(Ho, bands, band, ho0, ho1);                                                             \
   const int rowelems = W * C, orowelems = Wo * C;                                                        \
   const float scc = sc[c], shc = sh[c];                                                                  \
   (void)red;
@@ -400,6 +411,15 @@ bool bn_pool_supported(int B, int C, int H, int W) { return C % kWave == 0 && H 
 int bn_pool_rows(int B, int C, int H, int W) {
   if (!bn_pool_supported(B, C, H, W)) return MRLA_EUNSUPPORTED;
   return B * pool_geo(B, C, H, W, kPS).bands;
+}
+
+int bn_pool_plan(int B, int C, int H, int W, int band, int* out) {
+  if (!bn_pool_supported(B, C, H, W)) return MRLA_EUNSUPPORTED;
+  const PoolGeo g = pool_geo(B, C, H, W, kPS);
+  if (band < 0 || band >= g.bands) return MRLA_EINVAL;
+  out[0] = g.Ho; out[1] = g.Wo; out[2] = g.bands; out[3] = g.nwaves;
+  pool_band_rows(g.Ho, g.bands, band, out[4], out[5]);
+  return MRLA_OK;
 }
 
 #define MRLA_POOL_DISPATCH(DT, CALL)     \

@@ -45,6 +45,21 @@ def test_argument_validation_without_a_gpu():
     assert lib.mrla_base_pmom_reduce(None, None, 2, 64, 3, 4, None) == _lib.EINVAL
     assert lib.mrla_light_pool_fused(None, None, None, None, None, None, 1, 64, 4, 4, _lib.BF16, _lib.NHWC, None) == _lib.EINVAL
     assert lib.mrla_bn_moment_rows(256, 256, 56, 56, _lib.NHWC) == 256 * 4 and lib.mrla_bn_moment_rows(8, 64, 7, 7, _lib.NCHW) == 8
+    # the stem tail's geometry query: 6 ints for one row band; refuses what mrla_bn_pool_rows refuses, a band the shape does not
+    # have and a missing result array
+    import ctypes
+    plan, P6 = (ctypes.c_int * 6)(), lambda a: ctypes.cast(a, ctypes.c_void_p)       # noqa: E731
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, _lib.BF16, _lib.NHWC, 7, P6(plan)) == _lib.OK and tuple(plan) == (56, 56, 8, 8, 49, 56)
+    assert lib.mrla_bn_pool_rows(4, 64, 112, 112, _lib.BF16, _lib.NHWC) == 4 * 8
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, _lib.BF16, _lib.NHWC, 8, P6(plan)) == _lib.EINVAL
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, _lib.BF16, _lib.NHWC, -1, P6(plan)) == _lib.EINVAL
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, _lib.BF16, _lib.NHWC, 0, None) == _lib.EINVAL
+    assert lib.mrla_bn_pool_plan(0, 64, 112, 112, _lib.BF16, _lib.NHWC, 0, P6(plan)) == _lib.EINVAL
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, 7, _lib.NHWC, 0, P6(plan)) == _lib.EINVAL
+    assert lib.mrla_bn_pool_plan(4, 64, 112, 112, _lib.BF16, 2, 0, P6(plan)) == _lib.EINVAL
+    for bad in ((4, 64, 112, 112, _lib.BF16, _lib.NCHW), (4, 96, 112, 112, _lib.BF16, _lib.NHWC), (4, 64, 1, 112, _lib.BF16, _lib.NHWC)):
+        assert lib.mrla_bn_pool_plan(*bad, 0, P6(plan)) == lib.mrla_bn_pool_rows(*bad) == _lib.EUNSUPPORTED
+    assert _lib.bn_pool_plan(1, 192, 30, 34, _lib.F16, 1) == (15, 17, 2, 5, 7, 15) and _lib.bn_pool_plan(1, 192, 30, 34, _lib.F16, 2) is None
     # 1x1-convolution GEMMs: workspace rows of the forward moments / the weight-gradient partial tiles, argument checks
     assert lib.mrla_conv1x1_rows(64, 512, 128, _lib.BF16) == 1 and lib.mrla_conv1x1_rows(64, 96, 64, _lib.BF16) == _lib.EUNSUPPORTED and lib.mrla_conv1x1_rows(48, 64, 64, _lib.BF16) > 0
     assert lib.mrla_conv1x1_wgrad_rows(256 * 56 * 56, 64, 256, _lib.BF16) == 256        # one 64x256 tile x 256 pixel ranges
