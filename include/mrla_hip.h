@@ -77,7 +77,9 @@ enum { MRLA_BN_NONE = 0, MRLA_BN_TRAIN = 1, MRLA_BN_EVAL = 2 };
  *           ranges too, nothing else changes for a caller.  mrla_tuning_row_ranges() was added.
  *           Additive since (no bump): every mrla_conv1x1_* entry point takes MRLA_F16 wherever it takes MRLA_BF16, with the
  *           same answers for the same (m, k, n) -- callers that pass MRLA_BF16 see no change -- and
- *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh;  mrla_bn_pool_plan was added.
+ *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh;  mrla_bn_pool_plan was added;
+ *           the five mrla_conv1x1_f32_* symbols (fp32 operands on the fp32-input MFMA) were added -- every mrla_conv1x1_*
+ *           entry point that takes a dtype goes on answering MRLA_EUNSUPPORTED for MRLA_F32.
  * A consumer compares mrla_abi_version() (what the loaded library was built from) against this constant before its
  * first call. */
 #define MRLA_ABI_VERSION 5
@@ -622,6 +624,31 @@ int mrla_conv1x1_wgrad_bn_dx_supported(int m, int k, int n, int dtype);
 int mrla_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb /*[n,3]*/,
                              int relu, const void* x, const void* wt /*[k,n]*/, void* dx /*[m,k]*/, float* part, void* dw,
                              int m, int k, int n, int dtype, int dw_dtype, void* stream);
+
+/* The three products for fp32 operands, for a recipe that trains without autocast (resnet/train.py:397-409): five ADDITIVE
+ * symbols, MRLA_ABI_VERSION stays 5, and every entry point above goes on refusing MRLA_F32.  They run on the exact
+ * fp32-input MFMA (v_mfma_f32_32x32x2_f32): each output is a sum of fused multiply-adds in fp32, one rounding per
+ * product (the forward: four interleaved chains summed pairwise), in a fixed order -- bit-reproducible from run to run.
+ *   mrla_conv1x1_f32_fwd:   y[m, n] = sum_k x[m, k] * w[n, k], x [m, k], y [m, n] written once;
+ *                           w_trans = 0: w is [n, k];  w_trans = 1: w is reduction-major, [k, n] -- the input gradient
+ *                           dx[m, k] = sum_n dy[m, n] * w[n, k] is mrla_conv1x1_f32_fwd(dy, w, 1, dx, NULL, m, n, k) on the
+ *                           module's own [n, k] weight, no transposed copy;
+ *                           mom_part [opt]: [rows, n, MRLA_GEMM_MOMENTS] records over the fp32 outputs as stored, rows =
+ *                           mrla_conv1x1_f32_rows(); mrla_bn_stats_fwd_rows merges them.  NULL: no records, the same y.
+ *   mrla_conv1x1_f32_wgrad: dw[n, k] = sum_m dy[m, n] * x[m, k];  part: scratch [rows, n, k] fp32 with rows =
+ *                           mrla_conv1x1_f32_wgrad_rows() (a fixed split of the pixels, no atomics), summed into dw.
+ *   mrla_conv1x1_f32_plan:  out[4] = kernel form (0, 1, 2: the weight slice of 64, 128, 256 out-channels resident in LDS,
+ *                           k <= 256; 4, 5: a slice of 64, 128 streamed through LDS in chunks of 64 k, k > 256), chunks of x
+ *                           in flight, workgroups, record rows.
+ * Supported: n % 64 == 0, k % 64 == 0, 64 <= k <= 2048, m >= 1, m * max(n, k) * 4 < 2^31 (and, for the forward, at most 65 535 weight slices of 64 - 256
+ * out-channels: n <= 4 194 240 at k = 256); MRLA_EUNSUPPORTED otherwise (from the queries too).  MRLA_EINVAL for non-positive dimensions, NULL pointers (mom_part excepted) and pointers that are not
+ * 16-byte aligned, before any launch. */
+int mrla_conv1x1_f32_rows(int m, int k, int n);
+int mrla_conv1x1_f32_plan(int m, int k, int n, int* out);
+int mrla_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y, float* mom_part /*[opt]*/, int m, int k, int n,
+                         void* stream);
+int mrla_conv1x1_f32_wgrad_rows(int m, int k, int n);
+int mrla_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int m, int k, int n, void* stream);
 
 /* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input

@@ -10,4 +10,7 @@ def __getattr__(name):
     if name in ("graphed_step", "GraphedStep", "replay_matches_eager", "capture_step", "GraphReplayMismatch"):
         from . import graphs
         return getattr(graphs, name)
+    if name == "fp32_gemms":       # the switch of the fp32 1x1-convolution GEMMs (functional.CONV1X1_F32), as a context manager
+        from . import functional
+        return functional.fp32_gemms
     raise AttributeError(f"module 'mrla_amd' has no attribute {name!r}")

@@ -104,6 +104,11 @@ SIGNATURES = {
     "mrla_conv1x1_fwd_affine": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_rows": [_I] * 4,
     "mrla_conv1x1_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "mrla_conv1x1_f32_rows": [_I] * 3,
+    "mrla_conv1x1_f32_plan": [_I, _I, _I, _P],
+    "mrla_conv1x1_f32_fwd": [_P, _P, _I, _P, _P, _I, _I, _I, _P],
+    "mrla_conv1x1_f32_wgrad_rows": [_I] * 3,
+    "mrla_conv1x1_f32_wgrad": [_P, _P, _P, _P, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_supported": [_I] * 4,
     "mrla_conv1x1_wgrad_bn": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_dx_supported": [_I] * 4,
@@ -168,6 +173,13 @@ def conv1x1_plan(m, k, n, addend=False, dtype=None):
     """(pixel blocks per workgroup, pipeline depth, workgroups, moment rows) of mrla_conv1x1_fwd[_add], or None."""
     out = (ctypes.c_int * 4)()
     rc = load().mrla_conv1x1_plan(m, k, n, BF16 if dtype is None else dtype, int(addend), ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
+def conv1x1_f32_plan(m, k, n):
+    """(kernel form, X chunks in flight, workgroups, moment rows) of mrla_conv1x1_f32_fwd, or None."""
+    out = (ctypes.c_int * 4)()
+    rc = load().mrla_conv1x1_f32_plan(m, k, n, ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 

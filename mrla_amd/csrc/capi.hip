@@ -756,6 +756,36 @@ int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
+// The fp32 GEMMs (conv1x1_f32.hip): symbols of their own -- the entry points above go on refusing MRLA_F32.
+int mrla_conv1x1_f32_rows(int m, int k, int n) {
+  if (m <= 0 || k <= 0 || n <= 0) return MRLA_EINVAL;
+  return conv1x1_f32_rows(m, k, n);
+}
+
+int mrla_conv1x1_f32_plan(int m, int k, int n, int* out) {
+  if (m <= 0 || k <= 0 || n <= 0 || !out) return MRLA_EINVAL;
+  return conv1x1_f32_plan(m, k, n, out);
+}
+
+int mrla_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y, float* mom_part, int m, int k, int n,
+                         void* stream) {
+  if (!x || !w || !y || m <= 0 || k <= 0 || n <= 0 || (w_trans != 0 && w_trans != 1)) return MRLA_EINVAL;
+  // every lane moves 16-byte pieces of x, w and y; a record is 16 bytes
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)mom_part) & 15) return MRLA_EINVAL;
+  return launch_conv1x1_f32_fwd(x, w, w_trans, y, mom_part, m, k, n, (hipStream_t)stream);
+}
+
+int mrla_conv1x1_f32_wgrad_rows(int m, int k, int n) {
+  if (m <= 0 || k <= 0 || n <= 0) return MRLA_EINVAL;
+  return conv1x1_f32_wgrad_rows(m, k, n);
+}
+
+int mrla_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int m, int k, int n, void* stream) {
+  if (!dy || !x || !part || !dw || m <= 0 || k <= 0 || n <= 0) return MRLA_EINVAL;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;   // (the reduction reads part in 16-byte pieces)
+  return launch_conv1x1_f32_wgrad(dy, x, part, dw, m, k, n, (hipStream_t)stream);
+}
+
 int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;

@@ -696,6 +696,11 @@ static int launch_wgrad(const void* dy, const void* x, float* part, void* dw, in
   return hip_status(hipGetLastError());
 }
 
+int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, int NK, hipStream_t st) {
+  hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<float>, dim3(NK / 64), dim3(256), 0, st, part, dw, splits, NK);
+  return hip_status(hipGetLastError());
+}
+
 int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,
                          hipStream_t st) {
   return launch_wgrad(dy, x, part, dw, dw_f32, M, K, N, dtype, st, nullptr);

@@ -223,6 +223,15 @@ int conv1x1_wgrad_bn_dx_supported(int M, int K, int N);
 int launch_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
                                const void* x, const void* wt, void* dx, float* part, void* dw, int dw_f32, int M, int K, int N,
                                int dtype, hipStream_t st);
+// (the fixed-order sum of fp32 partial tiles part[splits][NK] behind it, conv1x1_wgrad_reduce_kernel<float>, for other producers)
+int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, int NK, hipStream_t st);
+// conv1x1_f32.hip -- the same three products for fp32 operands on the exact fp32-input MFMA (32x32x2); w_trans: w is [K, N]
+int conv1x1_f32_rows(int M, int K, int N);
+int conv1x1_f32_plan(int M, int K, int N, int* out);
+int launch_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y, float* part, int M, int K, int N,
+                           hipStream_t st);
+int conv1x1_f32_wgrad_rows(int M, int K, int N);
+int launch_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int M, int K, int N, hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)

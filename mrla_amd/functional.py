@@ -70,6 +70,24 @@ WGRAD_BN = True   # a 1x1 GEMM convolution + BatchNorm2d pair is one autograd no
 #                   False: the two nodes and the per-pass route -- the same values bit for bit, kept for A/B runs and tests.
 
 
+CONV1X1_F32 = False   # an fp32 channels_last 1x1 convolution outside autocast (the recipe of resnet/train.py:397-409) runs on the
+#                        fp32-input MFMA GEMMs (mrla_conv1x1_f32_fwd / _wgrad): forward with the BatchNorm moment records, input
+#                        gradient on the weight as stored, weight gradient -- the strided downsamples included.  False (the
+#                        default): fp32 convolutions stay on the stock kernels, launch for launch as before; fp32_gemms() turns it
+#                        on for a block of code.  profiles/conv1x1_f32.md has the numbers a change of the default rests on.
+
+
+@contextlib.contextmanager
+def fp32_gemms(enabled=True):
+    """CONV1X1_F32 = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
+    global CONV1X1_F32
+    prev, CONV1X1_F32 = CONV1X1_F32, bool(enabled)
+    try:
+        yield
+    finally:
+        CONV1X1_F32 = prev
+
+
 WGRAD_BN_DX = True   # where the call site asks for it (conv_bn_act(..., fuse_dx=True): the bottleneck's conv3 and downsample) and
 #                      one workgroup tile of that GEMM covers all channels of both sides (n = 256, k = 64: stage 1), it forms the convolution's input gradient dx = dy w as well (mrla_conv1x1_wgrad_bn_dx):
 #                      dy, the largest tensor of the block, is neither written nor read back, and the input-gradient GEMM's
@@ -1592,7 +1610,8 @@ class WeightBank:
 
 
 class _Conv1x1Fn(torch.autograd.Function):
-    """y = conv2d(x, w) for a bias-free 1x1 stride-1 convolution of a channels_last bf16 or fp16 tensor, plus the partial
+    """y = conv2d(x, w) for a bias-free 1x1 stride-1 convolution of a channels_last bf16 or fp16 tensor (fp32 under CONV1X1_F32: the GEMMs of
+    conv1x1_f32.hip, mrla_conv1x1_f32_fwd / _wgrad, the same roles), plus the partial
     moment-record rows of y the following BatchNorm needs (mrla_conv1x1_fwd: MRLA_GEMM_MOMENTS records, one row per
     workgroup pixel range -- the resident-weight kernels and the K-streaming kernel of the wide reductions, k >= 512, both
     write them; `mrla_bn_stats_fwd_rows` merges them).  Shapes the GEMMs do not take (mrla_conv1x1_rows < 0) run the stock
@@ -1623,8 +1642,17 @@ class _Conv1x1Fn(torch.autograd.Function):
             if not w.is_contiguous():
                 w = w.contiguous()
         part = None
-        rows = L.load().mrla_conv1x1_rows(m, k, n, _DT[x.dtype])      # > 0: supported, that many moment-record rows; < 0: not taken
-        if rows >= 0:
+        # fp32 operands (CONV1X1_F32): the GEMMs of conv1x1_f32.hip; remembered for the backward, whatever the switch says then
+        ctx.f32 = (CONV1X1_F32 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.data_ptr() % 16 == 0
+                   and w.data_ptr() % 16 == 0)
+        rows = (L.load().mrla_conv1x1_f32_rows(m, k, n) if ctx.f32
+                else L.load().mrla_conv1x1_rows(m, k, n, _DT[x.dtype]))   # > 0: supported, that many moment-record rows; < 0: not taken
+        if ctx.f32 and rows > 0:
+            y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
+            if want_moments:
+                part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
+            _call("mrla_conv1x1_f32_fwd", (x.numel() + y.numel()) * 4, _ptr(x), _ptr(w), 0, _ptr(y), _ptr(part), m, k, n, st)
+        elif rows >= 0:
             y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
             if want_moments and rows > 0:
                 part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
@@ -1665,7 +1693,22 @@ class _Conv1x1Fn(torch.autograd.Function):
         if d_through is not None and (d_through.dtype != x.dtype or not d_through.is_contiguous(memory_format=_CL)
                                       or d_through.data_ptr() % 16):
             d_through = d_through.to(x.dtype).contiguous(memory_format=_CL)
-        if need_x and same and lib.mrla_conv1x1_rows(m, n, k, dt) >= 0:
+        if ctx.f32:
+            # fp32: dX on the weight as stored ([n, k] is reduction-major for this product: w_trans = 1, no transposed copy),
+            # dW straight into an fp32 [n, k]; the shortcut's gradient is added by the tail below
+            if need_x and same and lib.mrla_conv1x1_f32_rows(m, n, k) > 0:
+                gx = torch.empty_like(x)
+                _call("mrla_conv1x1_f32_bwd_data", (dy.numel() + gx.numel()) * 4, _ptr(dy), _ptr(w), 1, _ptr(gx), None, m, n, k,
+                      _stream(), entry="mrla_conv1x1_f32_fwd")
+                need_x = False
+            rows = lib.mrla_conv1x1_f32_wgrad_rows(m, k, n) if (need_w and same) else 0
+            if rows > 0:
+                part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
+                gw = torch.empty((n, k), dtype=torch.float32, device=x.device)
+                _call("mrla_conv1x1_f32_wgrad", (dy.numel() + x.numel()) * 4, _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), m, k, n,
+                      _stream())
+                need_w = False
+        elif need_x and same and lib.mrla_conv1x1_rows(m, n, k, dt) >= 0:
             gx = torch.empty_like(x)
             wt = w16t if w16t is not None else w.t().contiguous()
             if d_through is not None and SHORTCUT_ADDEND and lib.mrla_conv1x1_addend_supported(m, n, k, sh, sw, dt) == 1:
@@ -1689,7 +1732,7 @@ class _Conv1x1Fn(torch.autograd.Function):
             need_x = False
         # the weight gradient dW[n, k] = sum_m dY[m, n] * X[m, k]: one pass over both activations, per-workgroup partial
         # tiles summed by a second kernel (MIOpen: memset + atomics into fp32 + a cast kernel)
-        if need_w and same and w.dtype == x.dtype and ctx.wdtype in (x.dtype, torch.float32):
+        if need_w and same and not ctx.f32 and w.dtype == x.dtype and ctx.wdtype in (x.dtype, torch.float32):
             rows = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
             if rows > 0:
                 part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
@@ -1743,6 +1786,7 @@ class _SubCtx:
 
     def __init__(self):
         self.saved_tensors, self.needs_input_grad = (), ()
+        self.f32 = False            # (_ConvBnFn is a 16-bit node: never the fp32 GEMMs of _Conv1x1Fn)
 
     def set_materialize_grads(self, flag):
         pass
@@ -1929,13 +1973,15 @@ def conv1x1_applies(conv, x, strided=False):
     """True when `conv(x)` belongs on the HIP GEMMs: nn.Conv2d 1x1 / stride 1 / no bias, channels_last bf16 or fp16 input,
     and a shape the forward kernel (mrla_conv1x1_rows) or the weight-gradient kernel (mrla_conv1x1_wgrad_rows) takes.
     strided: the question is asked for a strided 1x1 convolution, which runs as the stride-1 GEMM on the subsampled input
-    (`x` is the full-size input; the pixel count is the subsampled one).  That question is answered for bf16 ONLY: a strided
+    (`x` is the full-size input; the pixel count is the subsampled one).  That question is answered for bf16, and for fp32 under CONV1X1_F32, ONLY: a strided
     fp16 downsample keeps its route -- one stock convolution on the subsampled input (conv_bn_act) -- although the kernels,
     the compact addend of mrla_conv1x1_fwd_addend included, take fp16 at the C ABI; the models do not reach them yet."""
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (1, 1) and (strided or conv.stride == (1, 1))
             and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None):
         return False
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in ((torch.bfloat16,) if strided else (torch.bfloat16, torch.float16))
+    f32 = (CONV1X1_F32 and x.dtype == torch.float32 and conv.weight.dtype == torch.float32
+           and not (x.is_cuda and torch.is_autocast_enabled("cuda")))     # (under autocast the convolution is a 16-bit one)
+    if not (x.is_cuda and x.dim() == 4 and (f32 or x.dtype in ((torch.bfloat16,) if strided else (torch.bfloat16, torch.float16)))
             and x.is_contiguous(memory_format=_CL)
             and x.data_ptr() % 16 == 0):               # (the kernels move 16-byte fragments)
         return False
@@ -1945,6 +1991,12 @@ def conv1x1_applies(conv, x, strided=False):
     if strided and strided != "pre":                       # ("pre": `x` is the subsampled input already)
         h, w = (h + conv.stride[0] - 1) // conv.stride[0], (w + conv.stride[1] - 1) // conv.stride[1]
     lib, m, n, dt = L.load(), b * h * w, conv.out_channels, _DT[x.dtype]
+    if f32:                     # as below: the forward kernel, or the weight-gradient kernel where a gradient is wanted
+        if conv.weight.data_ptr() % 16:
+            return False
+        if lib.mrla_conv1x1_f32_rows(m, k, n) > 0:
+            return True
+        return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_f32_wgrad_rows(m, k, n) > 0
     if lib.mrla_conv1x1_rows(m, k, n, dt) >= 0:
         return True
     return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, dt) > 0
@@ -1952,7 +2004,7 @@ def conv1x1_applies(conv, x, strided=False):
 
 def shortcut_subsample(downsample, x):
     """(sh, sw) when `downsample` is the strided 1x1 convolution + BatchNorm of a stage's first block
-    (resnet_mrla_light.py:196-199) and runs on the GEMMs for the block input `x` (bf16 only: conv1x1_applies), else None.
+    (resnet_mrla_light.py:196-199) and runs on the GEMMs for the block input `x` (bf16, or fp32 under CONV1X1_F32: conv1x1_applies), else None.
     The block then asks conv1 for
     the subsampled input (conv_bn_act(..., passthrough=True, subsample=...)) and hands it on with presampled=True."""
     if not (isinstance(downsample, torch.nn.Sequential) and len(downsample) == 2 and _strided_1x1(downsample[0])):
