@@ -625,6 +625,32 @@ int mrla_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, con
                              int relu, const void* x, const void* wt /*[k,n]*/, void* dx /*[m,k]*/, float* part, void* dw,
                              int m, int k, int n, int dtype, int dw_dtype, void* stream);
 
+/* Weight gradient of a 3x3 convolution, padding 1, dilation 1, groups 1, stride `stride` = 1 or 2 in both directions (three
+ * ADDITIVE symbols, MRLA_ABI_VERSION stays 5) -- the backward of the reference's conv3x3 call sites, which the reference
+ * leaves to cuDNN: conv2 of the bottleneck and both 3x3 convolutions of the basic block in
+ * resnet/models/resnet_mrla_light.py, and the same blocks of the mmdet backbone:
+ *     dw[n, kh, kw, c] = sum_{b, y, x} dy[b, y, x, n] * x[b, y*stride + kh - 1, x*stride + kw - 1, c]
+ *   x: [b, h, w, c] and dy: [b, ho, wo, n] channels_last activations of `dtype` (MRLA_BF16 or MRLA_F16), ho = (h-1)/stride + 1,
+ *   wo = (w-1)/stride + 1; taps outside an image contribute nothing (the row above an image is not the previous image's last);
+ *   dw: [n, 3, 3, c] -- a [n, c, 3, 3] tensor in channels_last memory format -- of dw_dtype: `dtype` or MRLA_F32 (the fp32
+ *   master weight's gradient directly), fp32 accumulation on the MFMA either way;
+ *   part: fp32 workspace [rows, n, 9, c] with rows = mrla_conv3x3_wgrad_rows(...): the per-workgroup partial tiles of the
+ *   fixed split over output rows, summed in ascending order by a second kernel.
+ * No atomics and no memset: every element of part and dw is written exactly once per call, nothing is read outside x and dy,
+ * and the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from a replayed graph.
+ * MRLA_EUNSUPPORTED unless c % 64 == 0, n % 64 == 0, stride is 1 or 2, dtype MRLA_BF16 or MRLA_F16 and
+ * b * h * w * max(c, n) * 2 < 2^31; any b, h, w >= 1 within that (odd sizes, maps smaller than the kernel).
+ * MRLA_EINVAL, decided on the host before anything is launched: a non-positive dimension or stride, a dtype code that is none,
+ * a NULL pointer (`out` included), a pointer that is not 16-byte aligned, a 16-bit dw_dtype other than dtype.  The queries
+ * answer the same code as the launch for the same arguments. */
+int mrla_conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int stride, int dtype);      /* rows of part (> 0), or a negative code */
+/* Host-side query, `out` is a HOST array of 6 ints: tile n, tile c, output rows (image rows of dy, numbered image after
+ * image) per split, LDS stages, splits (= mrla_conv3x3_wgrad_rows()), output tiles.  Split i takes the rows
+ * [i * out[2], min(b * ho, (i + 1) * out[2])). */
+int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out);
+int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w,
+                       int stride, int dtype, int dw_dtype, void* stream);
+
 /* The three products for fp32 operands, for a recipe that trains without autocast (resnet/train.py:397-409): five ADDITIVE
  * symbols, MRLA_ABI_VERSION stays 5, and every entry point above goes on refusing MRLA_F32.  They run on the exact
  * fp32-input MFMA (v_mfma_f32_32x32x2_f32): each output is a sum of fused multiply-adds in fp32, one rounding per

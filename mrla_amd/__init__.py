@@ -13,4 +13,7 @@ def __getattr__(name):
     if name == "fp32_gemms":       # the switch of the fp32 1x1-convolution GEMMs (functional.CONV1X1_F32), as a context manager
         from . import functional
         return functional.fp32_gemms
+    if name == "conv3x3_wgrad":    # the switch of the own 3x3 weight gradient (functional.CONV3X3_WGRAD), as a context manager
+        from . import functional
+        return functional.conv3x3_wgrad
     raise AttributeError(f"module 'mrla_amd' has no attribute {name!r}")

@@ -113,6 +113,9 @@ SIGNATURES = {
     "mrla_conv1x1_wgrad_bn": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_dx_supported": [_I] * 4,
     "mrla_conv1x1_wgrad_bn_dx": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "mrla_conv3x3_wgrad_rows": [_I] * 7,
+    "mrla_conv3x3_wgrad_plan": [_I] * 7 + [_P],
+    "mrla_conv3x3_wgrad": [_P, _P, _P, _P] + [_I] * 8 + [_P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],
     "mrla_weight_bank_refresh_dt": [_P, _I, _I, _I, _P],
     "mrla_reduce_rows": [_P, _P, _I, _I, _P],
@@ -187,6 +190,13 @@ def conv1x1_wgrad_plan(m, k, n, dtype=None):
     """(chunks per workgroup, LDS stages, tile n, tile k, splits, tiles) of mrla_conv1x1_wgrad, or None."""
     out = (ctypes.c_int * 6)()
     rc = load().mrla_conv1x1_wgrad_plan(m, k, n, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
+def conv3x3_wgrad_plan(b, c, n, h, w, stride, dtype=None):
+    """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_wgrad, or None."""
+    out = (ctypes.c_int * 6)()
+    rc = load().mrla_conv3x3_wgrad_plan(b, c, n, h, w, stride, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 

@@ -1,0 +1,295 @@
+// Weight gradient of a 3x3 convolution (padding 1, dilation 1, groups 1, stride s = 1 or 2) of channels_last bf16 or fp16
+// activations as nine split-pixel MFMA products that share the dY operand:
+//   dW[n, kh, kw, c] = sum_{b, y, x} dY[b, y, x, n] * X[b, y*s + kh - 1, x*s + kw - 1, c]
+// Reference: the backward of the bottleneck's conv2 (resnet/models/resnet_mrla_light.py, conv3x3 of Bottleneck), of both
+// 3x3 convolutions of the basic block, and of the same blocks in the mmdet backbone; the reference leaves it to cuDNN.
+//
+// The stock library's split-K solver for this gradient accumulates with atomics into a zero-filled buffer: not
+// reproducible from run to run, and wrong from the second replay of a captured graph at small batches.  Here, as in
+// conv1x1_wgrad.hip, a workgroup owns one output tile (64 n x 64 c x all nine taps: 144 accumulator registers per lane) and
+// a FIXED range of output rows (a row = one image row of dY; rows are numbered image after image); it writes its fp32 partial
+// tile to part[split][n][9][c] and a second kernel sums the splits in ascending order.  No atomics, no memset; every element
+// of part and dw is written exactly once per call, and the result is a function of the inputs and the shape alone.
+//
+// Borders without per-lane masks: a step takes R output rows of ONE image (or, for rows wider than a step, a piece of one
+// row) and keeps both operands in LDS as padded rasters.  dY pixel (ry, j) sits at tile row ry*PY + j, X pixel (ty, cx) --
+// input row yo0*s - 1 + ty, input column xo0*s - 1 + cx -- at tile row ty*PX + cx with PX = s*PY, so the X pixel that tap
+// (kh, kw) pairs with dY tile row p = ry*PY + j is X tile row (s*ry + kh)*PX + s*j + kw = s*p + s*(s-1)*PY*ry + kh*PX + kw:
+// a tap is a constant offset from a row the lane computes once per k-step (s*p itself at stride 1).  Everything in the
+// rasters that is no pixel of this step -- the pad columns of dY, X pixels outside the image, rows above the first and below the last row
+// of the image (NOT the neighbouring image's rows), the tail up to a multiple of 16 pixels -- is written as zeros by the
+// loader, whose every global load is predicated on the pixel's own coordinates: nothing is read outside x or dy.  The pad
+// pixels of dY multiply into nothing (9/7 of the MFMA work at a 7x7 map).
+//
+// The loader is register-staged (16-byte pieces, four in flight per lane) and synchronous; two workgroups per CU
+// (__launch_bounds__(256, 2), <= 80 KB of LDS each) overlap one's loads with the other's MFMAs.  Both MFMA operands are COLUMNS
+// of the pixel-major tiles, read with gfx950's transposing LDS read (4 pixels x 16 channels per 16 lanes, every lane its own
+// address -- which is what lets the X operand step by s pixels); 16-byte chunk ch of tile row r sits at chunk position
+// ch ^ (((r >> 1) & 1) << 2) (conv1x1_wgrad.hip's swizzle for 128-byte rows): conflict-free at stride 1, two-way on the X
+// raster at stride 2, whose half-wave reads every other row.  (Swapping rows 4..7 of every eight in pairs on top of it, which
+// by the bank rule spreads those four rows over the whole bank row, was measured: 12 - 18 % SLOWER at the three stride-2
+// shapes of ResNet-50, the stride-1 shapes unchanged; profiles/conv3x3_wgrad.md.  Not kept, the cause not established.)
+#include <algorithm>
+#include <type_traits>
+
+#include "conv1x1_elem.h"
+#include "mrla_device.h"
+#include "mrla_kernels.h"
+
+namespace mrla {
+namespace {
+
+typedef short c3_s16x4 __attribute__((ext_vector_type(4)));
+typedef c1_f32x16 c3_f32x16;
+typedef __attribute__((address_space(3))) c3_s16x4* c3_lds_s16x4_ptr;
+
+constexpr int kC3Tile = 64;             // output tile: 64 n x 64 c (x 9 taps)
+constexpr int kC3Waves = 4;             // 2 x 2 waves, a 32 x 32 block of each tap per wave
+constexpr int kC3Stages = 1;            // LDS stages: the second workgroup of the CU is the overlap
+constexpr int kC3Target = 2 * 256;      // workgroups: two per CU (the sibling's CU count)
+constexpr int kC3MaxKP1 = 128;          // dY raster rows of a step at stride 1: (128 + 128 + 2*60 + 3) * 128 B = 48 KB at most
+constexpr int kC3MaxKP2 = 96;           // ... at stride 2, where the X raster has four times the pixels: (96 + 4*96 + 2*48 + 3 + 7)
+                                        // * 128 B = 74 KB at most (c3_plan's xt_cap with py * rmax <= 96, py <= 48 where rmax >= 2)
+constexpr int kC3MaxPY = 60;            // dY raster pitch
+constexpr int kC3RowB = kC3Tile * 2;    // bytes of a tile row (one pixel, 64 channels)
+
+struct C3Plan {
+  int ok = 0;
+  int ho = 0, wo = 0;
+  int py = 0, ws = 0, nseg = 0, rmax = 0;      // raster pitch, output columns per segment, segments per row, rows per step
+  int kp_cap = 0, xt_cap = 0;                  // tile rows of the two rasters
+  int rows_per_split = 0, splits = 0, tiles = 0;
+};
+
+struct C3Args {
+  int b, h, w, ho, wo, c, n;
+  int py, ws, nseg, rmax, kp_cap;
+  int rows_per_split, splits, tiles_c;
+  float inv_py, inv_px;
+};
+
+__device__ __forceinline__ int c3_swz(int row) { return ((row >> 1) & 1) << 2; }
+__device__ __forceinline__ int c3_off(int row, int chunk) { return row * kC3RowB + ((chunk ^ c3_swz(row)) << 4); }
+
+// 32x32x16 operand: this lane's 4 channels (of the 16-lane group's 16) of tile rows r and r2, its pixel of the k-step's first
+// and second eight
+template <typename T>
+__device__ __forceinline__ typename Elem16<T>::x8 c3_frag(const unsigned char* tile, int r, int r2, int chunk, int sub) {
+  const c3_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((c3_lds_s16x4_ptr)(tile + c3_off(r, chunk) + sub));
+  const c3_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((c3_lds_s16x4_ptr)(tile + c3_off(r2, chunk) + sub));
+  return __builtin_bit_cast(typename Elem16<T>::x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// grid: tiles * splits workgroups, 256 threads; LDS = (kp_cap + xt_cap) * 128 bytes
+template <typename T, int S>
+__device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, const T* __restrict__ X, float* __restrict__ part,
+                                                   const C3Args& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  unsigned char* const ty_tile = smem_raw;
+  unsigned char* const tx_tile = smem_raw + a.kp_cap * kC3RowB;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tiles = (a.n / kC3Tile) * a.tiles_c;
+  const int split = blockIdx.x / tiles, tile = blockIdx.x - split * tiles;
+  const int tn = tile / a.tiles_c, tc = tile - tn * a.tiles_c;
+  const int n0 = tn * kC3Tile, c0 = tc * kC3Tile;
+  const int rows = a.b * a.ho;
+  const int r_begin = split * a.rows_per_split, r_end = min(rows, r_begin + a.rows_per_split);
+  const int PY = a.py, PX = S * a.py;
+
+  const int wn = wave >> 1, wc = wave & 1;
+  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+  const int krel = 8 * (g >> 1) + q;                       // this lane's pixel of a 16-pixel k-step (and +4)
+  const int colA = wn * 32 + 16 * (g & 1) + 4 * pp, colB = wc * 32 + 16 * (g & 1) + 4 * pp;
+  const int chA = colA >> 3, subA = ((colA >> 2) & 1) * 8, chB = colB >> 3, subB = ((colB >> 2) & 1) * 8;
+
+  c3_f32x16 acc[9];
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+  const int prow = tid >> 3, pch = tid & 7;                // the loader: 32 tile rows per pass, 8 pieces a row
+  const u32x4 zero4 = {0u, 0u, 0u, 0u};
+
+  for (int r = r_begin; r < r_end;) {
+    const int img = r / a.ho, yo0 = r - img * a.ho;
+    const int R = min(a.rmax, min(a.ho - yo0, r_end - r));
+    for (int seg = 0; seg < a.nseg; ++seg) {
+      const int xo0 = seg * a.ws, ws = min(a.ws, a.wo - xo0);
+      const int KP = (R * PY + 15) & ~15;
+      const int XT = S * KP + S * (S - 1) * PY * (R - 1) + 2 * PX + 3;
+      const int ty_need = S * (R - 1) + 3, cx_need = S * (ws - 1) + 3;      // X raster rows / columns some tap of this step reads
+      const int yi0 = yo0 * S - 1, xi0 = xo0 * S - 1;
+      __syncthreads();                                      // the previous step's reads are done
+      // ---- dY raster: rows [0, KP) ----
+      for (int p0 = 0; p0 < KP; p0 += 128) {
+        u32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int p = p0 + 32 * u + prow;
+          const int ry = (int)(((float)p + 0.5f) * a.inv_py), j = p - ry * PY;
+          v[u] = zero4;
+          if (p < KP && ry < R && j < ws)
+            v[u] = *reinterpret_cast<const u32x4*>(dY + ((size_t)((img * a.ho + yo0 + ry) * a.wo + xo0 + j) * a.n + n0 + pch * 8));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int p = p0 + 32 * u + prow;
+          if (p < KP) *reinterpret_cast<u32x4*>(ty_tile + c3_off(p, pch)) = v[u];
+        }
+      }
+      // ---- X raster: rows [0, XT) ----
+      for (int t0 = 0; t0 < XT; t0 += 128) {
+        u32x4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int t = t0 + 32 * u + prow;
+          const int ty = (int)(((float)t + 0.5f) * a.inv_px), cx = t - ty * PX;
+          const int yi = yi0 + ty, xi = xi0 + cx;
+          v[u] = zero4;
+          if (t < XT && ty < ty_need && cx < cx_need && yi >= 0 && yi < a.h && xi >= 0 && xi < a.w)
+            v[u] = *reinterpret_cast<const u32x4*>(X + ((size_t)((img * a.h + yi) * a.w + xi) * a.c + c0 + pch * 8));
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int t = t0 + 32 * u + prow;
+          if (t < XT) *reinterpret_cast<u32x4*>(tx_tile + c3_off(t, pch)) = v[u];
+        }
+      }
+      __syncthreads();
+      // ---- nine products over the step's pixels ----
+      for (int k0 = 0; k0 < KP; k0 += 16) {
+        const int k = k0 + krel;
+        const typename Elem16<T>::x8 fa = c3_frag<T>(ty_tile, k, k + 4, chA, subA);
+        // the X raster row of dY raster row p = ry*PY + j under tap (0, 0): (S*ry)*PX + S*j = S*p + S*(S-1)*PY*ry (the tail
+        // behind the step's last row, all zeros in dY, stays inside the raster with ry held at R - 1)
+        int xr = S * k, xr2 = S * (k + 4);
+        if (S > 1) {
+          xr += S * (S - 1) * PY * min((int)(((float)k + 0.5f) * a.inv_py), R - 1);
+          xr2 += S * (S - 1) * PY * min((int)(((float)k + 4.5f) * a.inv_py), R - 1);
+        }
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw) {
+            const typename Elem16<T>::x8 fb = c3_frag<T>(tx_tile, xr + kh * PX + kw, xr2 + kh * PX + kw, chB, subB);
+            Elem16<T>::mfma(acc[kh * 3 + kw], fa, fb);
+          }
+      }
+    }
+    r += R;
+  }
+
+  // ---- partial tile: D[i][j], j = lane % 32 (c) on the lane, i = 8*(e/4) + 4*(lane/32) + e%4 (n) in register e ----
+  float* po = part + (((size_t)split * a.n + n0 + wn * 32) * 9) * a.c + c0 + wc * 32 + (lane & 31);
+  const int hh = lane >> 5;
+#pragma unroll
+  for (int t = 0; t < 9; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) po[((size_t)(8 * (e >> 2) + 4 * hh + (e & 3)) * 9 + t) * a.c] = acc[t][e];
+#endif
+}
+
+template <typename T, int S>
+__global__ __launch_bounds__(kC3Waves* kWave, 2) void conv3x3_wgrad_kernel(const T* __restrict__ dY, const T* __restrict__ X,
+                                                                           float* __restrict__ part, C3Args a) {
+  conv3x3_wgrad_body<T, S>(dY, X, part, a);
+}
+
+// dW[e] = part[0][e] + part[1][e] + ... in ascending order of the split; a lane takes four consecutive outputs
+template <typename TO>
+__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* __restrict__ part, TO* __restrict__ dW,
+                                                                   int splits, int total4) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const float4* src = reinterpret_cast<const float4*>(part) + i;
+  float4 s = src[0];
+#pragma unroll 8
+  for (int k = 1; k < splits; ++k) {
+    const float4 v = src[(size_t)k * total4];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  }
+  TO* o = dW + (size_t)i * 4;
+  o[0] = from_f<TO>(s.x); o[1] = from_f<TO>(s.y); o[2] = from_f<TO>(s.z); o[3] = from_f<TO>(s.w);
+}
+
+// The raster of a step: whole output rows where one fits (pitch = the row + its pads), else pieces of one row; as many rows
+// as kC3MaxKP1 / kC3MaxKP2 raster pixels hold.  Splits over output rows so that the grid is two workgroups per CU.
+C3Plan c3_plan(int b, int c, int n, int h, int w, int s) {
+  C3Plan p;
+  if (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || (s != 1 && s != 2) || c % kC3Tile || n % kC3Tile) return p;
+  if ((unsigned long long)b * h * w * std::max(c, n) * 2 >= 1ull << 31) return p;
+  p.ho = (h - 1) / s + 1;
+  p.wo = (w - 1) / s + 1;
+  const int pad = s == 1 ? 2 : 1;                          // s*PY >= the X columns of a segment, s*(ws - 1) + 3
+  if (p.wo + pad <= kC3MaxPY) {
+    p.ws = p.wo; p.py = p.wo + pad; p.nseg = 1;
+    p.rmax = std::max(1, std::min(p.ho, (s == 1 ? kC3MaxKP1 : kC3MaxKP2) / p.py));
+  } else {
+    p.py = kC3MaxPY; p.ws = kC3MaxPY - pad; p.nseg = (p.wo + p.ws - 1) / p.ws;
+    p.rmax = 1;
+  }
+  p.kp_cap = (p.rmax * p.py + 15) & ~15;
+  p.xt_cap = (s * p.kp_cap + s * (s - 1) * p.py * (p.rmax - 1) + 2 * s * p.py + 3 + 7) & ~7;
+  p.tiles = (n / kC3Tile) * (c / kC3Tile);
+  const long long rows = (long long)b * p.ho;
+  const long long want = std::max<long long>(1, std::min<long long>(rows, (kC3Target + p.tiles - 1) / p.tiles));
+  p.rows_per_split = (int)((rows + want - 1) / want);
+  p.splits = (int)((rows + p.rows_per_split - 1) / p.rows_per_split);
+  p.ok = 1;
+  return p;
+}
+
+template <typename T, int S>
+int c3_launch(const C3Plan& p, const C3Args& a, const void* dy, const void* x, float* part, hipStream_t st) {
+  const size_t lds = (size_t)(p.kp_cap + p.xt_cap) * kC3RowB;
+  if (lds > 80 * 1024) return MRLA_EUNSUPPORTED;
+  if (lds_opt_in(reinterpret_cast<const void*>(conv3x3_wgrad_kernel<T, S>), lds) != hipSuccess) return MRLA_EHIP;
+  hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, S>), dim3(p.tiles * p.splits), dim3(kC3Waves * kWave), lds, st, (const T*)dy,
+                     (const T*)x, part, a);
+  return MRLA_OK;
+}
+
+}  // namespace
+
+int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s) {
+  const C3Plan p = c3_plan(b, c, n, h, w, s);
+  return p.ok ? p.splits : MRLA_EUNSUPPORTED;
+}
+
+// {tile n, tile c, output rows per split, LDS stages, splits, output tiles}
+int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out) {
+  const C3Plan p = c3_plan(b, c, n, h, w, s);
+  if (!p.ok) return MRLA_EUNSUPPORTED;
+  out[0] = kC3Tile; out[1] = kC3Tile; out[2] = p.rows_per_split; out[3] = kC3Stages; out[4] = p.splits; out[5] = p.tiles;
+  return MRLA_OK;
+}
+
+int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
+                         int s, int dtype, hipStream_t st) {
+  const C3Plan p = c3_plan(b, c, n, h, w, s);
+  if (!p.ok || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
+  C3Args a;
+  a.b = b; a.h = h; a.w = w; a.ho = p.ho; a.wo = p.wo; a.c = c; a.n = n;
+  a.py = p.py; a.ws = p.ws; a.nseg = p.nseg; a.rmax = p.rmax; a.kp_cap = p.kp_cap;
+  a.rows_per_split = p.rows_per_split; a.splits = p.splits; a.tiles_c = c / kC3Tile;
+  a.inv_py = 1.0f / (float)p.py; a.inv_px = 1.0f / (float)(s * p.py);
+  int rc;
+  if (dtype == MRLA_F16)
+    rc = s == 1 ? c3_launch<f16_t, 1>(p, a, dy, x, part, st) : c3_launch<f16_t, 2>(p, a, dy, x, part, st);
+  else
+    rc = s == 1 ? c3_launch<bf16_t, 1>(p, a, dy, x, part, st) : c3_launch<bf16_t, 2>(p, a, dy, x, part, st);
+  if (rc != MRLA_OK) return rc;
+  const int total4 = n * 9 * c / 4;
+  const dim3 grid((total4 + 255) / 256), block(256);
+  if (dw_f32)      // the fp32 master weight's gradient directly
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<float>, grid, block, 0, st, part, (float*)dw, p.splits, total4);
+  else if (dtype == MRLA_F16)
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<f16_t>, grid, block, 0, st, part, (f16_t*)dw, p.splits, total4);
+  else
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<bf16_t>, grid, block, 0, st, part, (bf16_t*)dw, p.splits, total4);
+  return hip_status(hipGetLastError());
+}
+
+}  // namespace mrla

@@ -225,6 +225,12 @@ int launch_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, c
                                int dtype, hipStream_t st);
 // (the fixed-order sum of fp32 partial tiles part[splits][NK] behind it, conv1x1_wgrad_reduce_kernel<float>, for other producers)
 int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, int NK, hipStream_t st);
+// conv3x3_wgrad.hip -- the weight gradient of a 3x3 / padding 1 / stride s (1 or 2) convolution, dW [n,3,3,c], as nine such
+// products over padded rasters of one image's rows (bf16 or fp16); part [rows][n][9][c]
+int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s);
+int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
+int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
+                         int s, int dtype, hipStream_t st);
 // conv1x1_f32.hip -- the same three products for fp32 operands on the exact fp32-input MFMA (32x32x2); w_trans: w is [K, N]
 int conv1x1_f32_rows(int M, int K, int N);
 int conv1x1_f32_plan(int M, int K, int N, int* out);

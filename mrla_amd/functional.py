@@ -88,6 +88,26 @@ def fp32_gemms(enabled=True):
         CONV1X1_F32 = prev
 
 
+CONV3X3_WGRAD = False   # the weight gradient of an eligible 3x3 convolution (conv3x3_applies: the bottleneck's conv2, both of the
+#                         basic block's) comes from mrla_conv3x3_wgrad -- fixed split, fixed summation order, no atomics:
+#                         bit-reproducible, and right under graph replay at the small batches where the stock library's
+#                         split-K solver is not -- written straight as the fp32 master weight's gradient.  Forward and input
+#                         gradient stay the stock operator's.  False (the default): conv(x) itself, the very same autograd
+#                         graph and launches as before; conv3x3_wgrad() turns it on for a block of code.
+#                         profiles/conv3x3_wgrad.md has the numbers a change of the default rests on.
+
+
+@contextlib.contextmanager
+def conv3x3_wgrad(enabled=True):
+    """CONV3X3_WGRAD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
+    global CONV3X3_WGRAD
+    prev, CONV3X3_WGRAD = CONV3X3_WGRAD, bool(enabled)
+    try:
+        yield
+    finally:
+        CONV3X3_WGRAD = prev
+
+
 WGRAD_BN_DX = True   # where the call site asks for it (conv_bn_act(..., fuse_dx=True): the bottleneck's conv3 and downsample) and
 #                      one workgroup tile of that GEMM covers all channels of both sides (n = 256, k = 64: stage 1), it forms the convolution's input gradient dx = dy w as well (mrla_conv1x1_wgrad_bn_dx):
 #                      dy, the largest tensor of the block, is neither written nor read back, and the input-gradient GEMM's
@@ -2000,6 +2020,90 @@ def conv1x1_applies(conv, x, strided=False):
     if lib.mrla_conv1x1_rows(m, k, n, dt) >= 0:
         return True
     return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, dt) > 0
+
+
+def _conv3x3_dtype(x):
+    """The dtype the stock convolution of `x` computes in: autocast's under CUDA autocast, else x's own."""
+    if x.is_cuda and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return x.dtype
+
+
+def conv3x3_applies(conv, x):
+    """True when the weight gradient of `conv(x)` belongs on mrla_conv3x3_wgrad: a bias-free nn.Conv2d 3x3 / padding 1 /
+    dilation 1 / groups 1 / stride (1, 1) or (2, 2) whose weight wants its gradient, a CUDA channels_last input that the
+    convolution computes in bf16 or fp16 (its own dtype, or autocast's), and a shape the kernel takes (mrla_conv3x3_wgrad_rows).
+    Frozen stages, ResNeXt groups, dilated detection variants, NCHW and fp32 keep the stock path."""
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride in ((1, 1), (2, 2))
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.padding_mode == "zeros"):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
+        return False
+    wt = conv.weight
+    if not (torch.is_grad_enabled() and wt.requires_grad and wt.is_cuda and x.shape[1] == conv.in_channels):
+        return False
+    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
+    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
+        return False
+    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+        return False
+    b, c, h, w = x.shape
+    return L.load().mrla_conv3x3_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
+
+
+class _Conv3x3Fn(torch.autograd.Function):
+    """y = conv2d(x, w, stride, padding 1) of a channels_last bf16 or fp16 `x` by the stock operator, on `w` cast to x's dtype as
+    autocast casts it.  Backward: dX from the stock operator's backward with the weight gradient masked out (its split-K
+    weight-gradient solver is never invoked), dW [n, 3, 3, c] from mrla_conv3x3_wgrad in the weight's own dtype -- for an fp32
+    master weight the fp32 sums themselves, no 16-bit rounding and no cast kernel -- returned as [n, c, 3, 3]."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, x, w, stride):
+        ctx.stride = (stride, stride)
+        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
+        w16 = w if w.dtype == x.dtype else w.to(x.dtype)
+        ctx.save_for_backward(x, w16)
+        return torch.ops.aten.convolution(x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1)
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, dy):
+        x, w16 = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy = dy.contiguous(memory_format=_CL)
+        b, c, h, wd = x.shape
+        n = w16.shape[0]
+        gx = gw = None
+        if need_w and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
+            dt = _DT[x.dtype]
+            rows = L.load().mrla_conv3x3_wgrad_rows(b, c, n, h, wd, ctx.stride[0], dt)
+            if rows > 0:
+                part = torch.empty((rows, n, 9, c), dtype=torch.float32, device=x.device)
+                gw = torch.empty((n, c, 3, 3), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
+                _call("mrla_conv3x3_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
+                      b, c, n, h, wd, ctx.stride[0], dt, _DT[ctx.wdtype], _stream())
+                need_w = False
+        if need_x or need_w:
+            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1,
+                                                              [need_x, need_w, False])
+            gx = gx2 if need_x else None
+            gw = gw2.to(ctx.wdtype) if need_w else gw
+        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
+            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
+        return gx, gw, None
+
+
+def conv3x3(x, conv):
+    """conv(x) for the 3x3 convolutions of the blocks (resnet_mrla_light.py: conv2 of the bottleneck, both of the basic
+    block).  With CONV3X3_WGRAD off, or where conv3x3_applies says no, it IS conv(x): the same autograd graph as before.
+    Otherwise one autograd node whose forward and input gradient are the stock operator's and whose weight gradient is
+    mrla_conv3x3_wgrad's."""
+    if not (CONV3X3_WGRAD and conv3x3_applies(conv, x)):
+        return conv(x)
+    dt = _conv3x3_dtype(x)
+    return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0])
 
 
 def shortcut_subsample(downsample, x):
