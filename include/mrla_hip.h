@@ -651,6 +651,32 @@ int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int d
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w,
                        int stride, int dtype, int dw_dtype, void* stream);
 
+/* Weight gradient of the stem convolution: 7x7, stride 2, padding 3, dilation 1, groups 1, three input channels (three
+ * ADDITIVE symbols, MRLA_ABI_VERSION stays 5) -- the backward of conv1 of resnet/models/resnet_mrla_light.py, which the
+ * reference leaves to cuDNN:
+ *     dw[n, kh, kw, c] = sum_{b, y, x} dy[b, y, x, n] * x[b, 2y + kh - 3, 2x + kw - 3, c]        kh, kw in 0..6, c in 0..2
+ *   x: [b, h, w, 3] and dy: [b, ho, wo, n] channels_last activations of `dtype` (MRLA_BF16 or MRLA_F16), ho = (h-1)/2 + 1,
+ *   wo = (w-1)/2 + 1; taps outside an image contribute nothing (the row above an image is not the previous image's last);
+ *   dw: [n, 7, 7, 3] -- a [n, 3, 7, 7] tensor in channels_last memory format -- of dw_dtype: `dtype` or MRLA_F32 (the fp32
+ *   master weight's gradient directly), fp32 accumulation on the MFMA either way;
+ *   part: fp32 workspace [rows, n, 7, 7, 3] with rows = mrla_stem_conv_wgrad_rows(...): the per-workgroup partial tiles of
+ *   the fixed split over output rows, summed in ascending order by a second kernel.
+ * No atomics and no memset: every element of part and dw is written exactly once per call, nothing is read outside x and dy,
+ * and the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from a replayed graph.
+ * MRLA_EUNSUPPORTED unless n % 64 == 0, dtype MRLA_BF16 or MRLA_F16 and b * h * w * max(3, n) * 2 < 2^31; any b, h, w >= 1
+ * within that: odd heights, ODD WIDTHS (served, on 2-byte loads of x where even widths use 4-byte loads), maps smaller than
+ * the kernel, rows wider than one step (cut into column segments).
+ * MRLA_EINVAL, decided on the host before anything is launched: a non-positive dimension, a dtype code that is none, a NULL
+ * pointer (`out` included), a pointer that is not 16-byte aligned, a 16-bit dw_dtype other than dtype.  The queries answer
+ * the same code as the launch for the same arguments. */
+int mrla_stem_conv_wgrad_rows(int b, int n, int h, int w, int dtype);      /* rows of part (> 0), or a negative code */
+/* Host-side query, `out` is a HOST array of 7 ints: tile n, output rows (image rows of dy, numbered image after image) per
+ * split, splits (= mrla_stem_conv_wgrad_rows()), column segments per row, LDS bytes of a workgroup (<= 65536), output columns
+ * per segment, output rows per step.  Split i takes the rows [i * out[1], min(b * ho, (i + 1) * out[1])). */
+int mrla_stem_conv_wgrad_plan(int b, int n, int h, int w, int dtype, int* out);
+int mrla_stem_conv_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int n, int h, int w, int dtype,
+                         int dw_dtype, void* stream);
+
 /* The three products for fp32 operands, for a recipe that trains without autocast (resnet/train.py:397-409): five ADDITIVE
  * symbols, MRLA_ABI_VERSION stays 5, and every entry point above goes on refusing MRLA_F32.  They run on the exact
  * fp32-input MFMA (v_mfma_f32_32x32x2_f32): each output is a sum of fused multiply-adds in fp32, one rounding per

@@ -16,4 +16,10 @@ def __getattr__(name):
     if name == "conv3x3_wgrad":    # the switch of the own 3x3 weight gradient (functional.CONV3X3_WGRAD), as a context manager
         from . import functional
         return functional.conv3x3_wgrad
+    if name == "stem_wgrad":       # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
+        from . import functional
+        return functional.stem_wgrad
+    if name == "reproducible_gradients":      # both of them: every parameter gradient a function of the step's inputs alone
+        from . import functional
+        return functional.reproducible_gradients
     raise AttributeError(f"module 'mrla_amd' has no attribute {name!r}")

@@ -788,6 +788,37 @@ int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv3x3_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
 }
 
+// The stem's 7x7 / stride 2 weight gradient (stem_wgrad.hip).  One argument check for the two queries and the launch, as above.
+static int stem_conv_wgrad_args(int b, int n, int h, int w, int dtype) {
+  if (b <= 0 || n <= 0 || h <= 0 || w <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return MRLA_OK;
+}
+
+int mrla_stem_conv_wgrad_rows(int b, int n, int h, int w, int dtype) {
+  const int rc = stem_conv_wgrad_args(b, n, h, w, dtype);
+  return rc != MRLA_OK ? rc : stem_conv_wgrad_rows(b, n, h, w);
+}
+
+int mrla_stem_conv_wgrad_plan(int b, int n, int h, int w, int dtype, int* out) {
+  if (!out) return MRLA_EINVAL;
+  const int rc = stem_conv_wgrad_args(b, n, h, w, dtype);
+  return rc != MRLA_OK ? rc : stem_conv_wgrad_plan(b, n, h, w, out);
+}
+
+int mrla_stem_conv_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int n, int h, int w, int dtype,
+                         int dw_dtype, void* stream) {
+  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
+  // a lane moves 16 bytes of dy and part, aligned dwords of x, and four elements of dw
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  const int rc = stem_conv_wgrad_args(b, n, h, w, dtype);
+  if (rc == MRLA_EINVAL) return rc;
+  if (dw_dtype != MRLA_F32 && dw_dtype != dtype) return MRLA_EINVAL;
+  if (rc != MRLA_OK) return rc;
+  return launch_stem_conv_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, b, n, h, w, dtype, (hipStream_t)stream);
+}
+
 // The fp32 GEMMs (conv1x1_f32.hip): symbols of their own -- the entry points above go on refusing MRLA_F32.
 int mrla_conv1x1_f32_rows(int m, int k, int n) {
   if (m <= 0 || k <= 0 || n <= 0) return MRLA_EINVAL;

@@ -231,6 +231,12 @@ int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
                          int s, int dtype, hipStream_t st);
+// stem_wgrad.hip -- the weight gradient of the stem's 7x7 / stride 2 / padding 3 convolution of three channels, dW [n,7,7,3],
+// as one product of dY^T and the pixels' seven 21-element windows (bf16 or fp16); part [rows][n][7][7][3]
+int stem_conv_wgrad_rows(int b, int n, int h, int w);
+int stem_conv_wgrad_plan(int b, int n, int h, int w, int* out);
+int launch_stem_conv_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int n, int h, int w,
+                           int dtype, hipStream_t st);
 // conv1x1_f32.hip -- the same three products for fp32 operands on the exact fp32-input MFMA (32x32x2); w_trans: w is [K, N]
 int conv1x1_f32_rows(int M, int K, int N);
 int conv1x1_f32_plan(int M, int K, int N, int* out);

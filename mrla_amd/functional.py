@@ -108,7 +108,34 @@ def conv3x3_wgrad(enabled=True):
         CONV3X3_WGRAD = prev
 
 
-WGRAD_BN_DX = True   # where the call site asks for it (conv_bn_act(..., fuse_dx=True): the bottleneck's conv3 and downsample) and
+STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolution of three channels (stem_conv_applies: conv1 of
+#                      ResNet_mrlal) comes from mrla_stem_conv_wgrad -- fixed split, fixed summation order, no atomics --
+#                      written straight as the fp32 master weight's gradient.  The forward stays the stock operator's; the
+#                      image batch needs no gradient.  False (the default): conv(x) itself, the very same autograd graph and
+#                      launches as before; stem_wgrad() turns it on for a block of code.  profiles/stem_wgrad.md has the
+#                      numbers a change of the default rests on.
+
+
+@contextlib.contextmanager
+def stem_wgrad(enabled=True):
+    """STEM_WGRAD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
+    global STEM_WGRAD
+    prev, STEM_WGRAD = STEM_WGRAD, bool(enabled)
+    try:
+        yield
+    finally:
+        STEM_WGRAD = prev
+
+
+@contextlib.contextmanager
+def reproducible_gradients(enabled=True):
+    """CONV3X3_WGRAD and STEM_WGRAD = `enabled` inside the block: with both on no weight gradient of a resnet*_mrlal step is
+    left to an atomic split-K solver.  The previous values come back on exit, also when the block raises."""
+    with conv3x3_wgrad(enabled), stem_wgrad(enabled):
+        yield
+
+
+WGRAD_BN_DX = True  # where the call site asks for it (conv_bn_act(..., fuse_dx=True): the bottleneck's conv3 and downsample) and
 #                      one workgroup tile of that GEMM covers all channels of both sides (n = 256, k = 64: stage 1), it forms the convolution's input gradient dx = dy w as well (mrla_conv1x1_wgrad_bn_dx):
 #                      dy, the largest tensor of the block, is neither written nor read back, and the input-gradient GEMM's
 #                      launch is gone.  False: mrla_conv1x1_wgrad_bn and the input-gradient GEMM -- the same values bit for bit,
@@ -2104,6 +2131,82 @@ def conv3x3(x, conv):
         return conv(x)
     dt = _conv3x3_dtype(x)
     return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0])
+
+
+def stem_conv_applies(conv, x):
+    """True when the weight gradient of `conv(x)` belongs on mrla_stem_conv_wgrad: a bias-free nn.Conv2d 7x7 / stride (2, 2) /
+    padding (3, 3) / dilation 1 / groups 1 of three input channels whose weight wants its gradient, a CUDA channels_last
+    16-byte-aligned input that the convolution computes in bf16 or fp16 (its own dtype, or autocast's), and a shape the kernel
+    takes (mrla_stem_conv_wgrad_rows).  Everything else keeps the stock path."""
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
+            and conv.in_channels == 3):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
+        return False
+    wt = conv.weight
+    if not (torch.is_grad_enabled() and wt.requires_grad and wt.is_cuda and x.shape[1] == 3):
+        return False
+    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
+    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
+        return False
+    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+        return False
+    b, _, h, w = x.shape
+    return L.load().mrla_stem_conv_wgrad_rows(b, conv.out_channels, h, w, _DT[dt]) > 0
+
+
+class _StemConvFn(torch.autograd.Function):
+    """y = conv2d(x, w, stride 2, padding 3) of a channels_last bf16 or fp16 three-channel `x` by the stock operator, on `w`
+    cast to x's dtype as autocast casts it.  Backward: dW [n, 7, 7, 3] from mrla_stem_conv_wgrad in the weight's own dtype --
+    for an fp32 master weight the fp32 sums themselves -- returned as [n, 3, 7, 7] with the weight's strides.  The stock
+    backward runs only for what is left: dX if `x` itself needs a gradient (the image batch does not), and dW where dy arrives
+    in another dtype or misaligned."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, x, w):
+        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
+        w16 = w if w.dtype == x.dtype else w.to(x.dtype)
+        ctx.save_for_backward(x, w16)
+        return torch.ops.aten.convolution(x, w16, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1)
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, dy):
+        x, w16 = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy = dy.contiguous(memory_format=_CL)
+        b, _, h, wd = x.shape
+        n = w16.shape[0]
+        gx = gw = None
+        if need_w and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
+            dt = _DT[x.dtype]
+            rows = L.load().mrla_stem_conv_wgrad_rows(b, n, h, wd, dt)
+            if rows > 0:
+                part = torch.empty((rows, n, 147), dtype=torch.float32, device=x.device)
+                gw = torch.empty((n, 3, 7, 7), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
+                _call("mrla_stem_conv_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
+                      b, n, h, wd, dt, _DT[ctx.wdtype], _stream())
+                need_w = False
+        if need_x or need_w:
+            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
+                                                              [need_x, need_w, False])
+            gx = gx2 if need_x else None
+            gw = gw2.to(ctx.wdtype) if need_w else gw
+        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
+            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
+        return gx, gw
+
+
+def stem_conv(x, conv):
+    """conv(x) for the stem's 7x7 / stride 2 convolution (resnet_mrla_light.py: conv1).  With STEM_WGRAD off, or where
+    stem_conv_applies says no, it IS conv(x): the same autograd graph as before.  Otherwise one autograd node whose forward is
+    the stock operator's and whose weight gradient is mrla_stem_conv_wgrad's."""
+    if not (STEM_WGRAD and stem_conv_applies(conv, x)):
+        return conv(x)
+    dt = _conv3x3_dtype(x)
+    return _StemConvFn.apply(x if x.dtype == dt else x.to(dt), conv.weight)
 
 
 def shortcut_subsample(downsample, x):

@@ -319,7 +319,7 @@ class ResNet_mrlal(_ResNetMRLA):
         if self.channels_last and x.is_cuda:
             x = _to_channels_last(x)
         with F_.batched_bookkeeping(self._stochastic_depth_blocks(), self._weight_bank() if x.is_cuda else None):
-            x = F_.bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)
+            x = F_.bn_relu_maxpool(F_.stem_conv(x, self.conv1), self.bn1, self.maxpool)
             return self.layer4(self.layer3(self.layer2(self.layer1(x))))
 
 
