@@ -651,6 +651,34 @@ int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int d
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w,
                        int stride, int dtype, int dw_dtype, void* stream);
 
+/* Forward of that 3x3 convolution, padding 1, dilation 1, groups 1, stride `stride` = 1 or 2 in both directions, as an implicit
+ * GEMM on the MFMA with the BatchNorm moment records of its outputs (three ADDITIVE symbols, MRLA_ABI_VERSION stays 5) --
+ * the reference's conv3x3 call sites themselves, which the reference leaves to cuDNN:
+ *     y[b, yo, xo, n] = round( sum_{kh, kw, c} x[b, yo*stride + kh - 1, xo*stride + kw - 1, c] * wt[n, kh, kw, c] )
+ *   x: [b, h, w, c] and y: [b, ho, wo, n] channels_last activations of `dtype` (MRLA_BF16 or MRLA_F16), ho = (h-1)/stride + 1,
+ *   wo = (w-1)/stride + 1; taps outside an image contribute nothing (the row above an image is not the previous image's last);
+ *   wt: [n, 3, 3, c] of `dtype` -- a [n, c, 3, 3] weight in channels_last memory format; fp32 accumulation over all nine taps
+ *   and all of c in one fixed order (no split of the reduction), ONE rounding to nearest even at the store;
+ *   mom_part [opt]: fp32 records [rows, n, MRLA_GEMM_MOMENTS] with rows = mrla_conv3x3_fwd_rows(...): per (workgroup range of
+ *   output rows, channel) sum (y - p), sum (y - p)^2, the pivot p (the range's first output of the channel) and the pixel
+ *   count, over the ROUNDED outputs -- what mrla_bn_stats_fwd_rows merges.  NULL: no records, the same y bit for bit.
+ * The input gradient at stride 1 is the same call: mrla_conv3x3_fwd(dy, wflip, dx, NULL, b, n, c, h, w, 1, dtype, stream) with
+ * wflip[c, kh, kw, n] = wt[n, 2-kh, 2-kw, c].
+ * No atomics and no memset: every element of y and mom_part is written exactly once per call, nothing is read outside x and
+ * wt, and the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from a replayed graph.
+ * MRLA_EUNSUPPORTED unless c % 64 == 0, n % 64 == 0, stride is 1 or 2, dtype MRLA_BF16 or MRLA_F16 and
+ * b * h * w * max(c, n) * 2 < 2^31; any b, h, w >= 1 within that (odd sizes, maps smaller than the kernel, rows wider than a
+ * step).  MRLA_EINVAL, decided on the host before anything is launched: a non-positive dimension or stride, a dtype code that
+ * is none, a NULL x, wt, y or `out`, a pointer (mom_part included) that is not 16-byte aligned.  The queries answer the same
+ * code as the launch for the same arguments. */
+int mrla_conv3x3_fwd_rows(int b, int c, int n, int h, int w, int stride, int dtype);      /* rows of mom_part (> 0), or a negative code */
+/* Host-side query, `out` is a HOST array of 6 ints: tile n, output rows (image rows of y, numbered image after image) per
+ * workgroup range, output rows per step, column segments per row, record rows (= mrla_conv3x3_fwd_rows()), workgroups.
+ * Range i takes the rows [i * out[1], min(b * ho, (i + 1) * out[1])); a workgroup is one (range, 64-channel tile). */
+int mrla_conv3x3_fwd_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out);
+int mrla_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom_part /*[opt]*/, int b, int c, int n, int h, int w,
+                     int stride, int dtype, void* stream);
+
 /* Weight gradient of the stem convolution: 7x7, stride 2, padding 3, dilation 1, groups 1, three input channels (three
  * ADDITIVE symbols, MRLA_ABI_VERSION stays 5) -- the backward of conv1 of resnet/models/resnet_mrla_light.py, which the
  * reference leaves to cuDNN:

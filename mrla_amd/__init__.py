@@ -16,6 +16,9 @@ def __getattr__(name):
     if name == "conv3x3_wgrad":    # the switch of the own 3x3 weight gradient (functional.CONV3X3_WGRAD), as a context manager
         from . import functional
         return functional.conv3x3_wgrad
+    if name == "conv3x3_fwd":      # the switch of the own 3x3 forward and stride-1 input gradient (functional.CONV3X3_FWD)
+        from . import functional
+        return functional.conv3x3_fwd
     if name == "stem_wgrad":       # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
         from . import functional
         return functional.stem_wgrad

@@ -116,6 +116,9 @@ SIGNATURES = {
     "mrla_conv3x3_wgrad_rows": [_I] * 7,
     "mrla_conv3x3_wgrad_plan": [_I] * 7 + [_P],
     "mrla_conv3x3_wgrad": [_P, _P, _P, _P] + [_I] * 8 + [_P],
+    "mrla_conv3x3_fwd_rows": [_I] * 7,
+    "mrla_conv3x3_fwd_plan": [_I] * 7 + [_P],
+    "mrla_conv3x3_fwd": [_P, _P, _P, _P] + [_I] * 7 + [_P],
     "mrla_stem_conv_wgrad_rows": [_I] * 5,
     "mrla_stem_conv_wgrad_plan": [_I] * 5 + [_P],
     "mrla_stem_conv_wgrad": [_P, _P, _P, _P] + [_I] * 6 + [_P],
@@ -200,6 +203,14 @@ def conv3x3_wgrad_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_wgrad, or None."""
     out = (ctypes.c_int * 6)()
     rc = load().mrla_conv3x3_wgrad_plan(b, c, n, h, w, stride, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
+def conv3x3_fwd_plan(b, c, n, h, w, stride, dtype=None):
+    """(tile n, output rows per workgroup, rows per step, segments per row, record rows, workgroups) of mrla_conv3x3_fwd, or
+    None."""
+    out = (ctypes.c_int * 6)()
+    rc = load().mrla_conv3x3_fwd_plan(b, c, n, h, w, stride, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
     return tuple(out) if rc == OK else None
 
 

@@ -788,6 +788,28 @@ int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv3x3_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
 }
 
+// The 3x3 forward (conv3x3_fwd.hip).  The argument check is the weight gradient's: one code from the queries and the launch.
+int mrla_conv3x3_fwd_rows(int b, int c, int n, int h, int w, int stride, int dtype) {
+  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  return rc != MRLA_OK ? rc : conv3x3_fwd_rows(b, c, n, h, w, stride);
+}
+
+int mrla_conv3x3_fwd_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out) {
+  if (!out) return MRLA_EINVAL;
+  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  return rc != MRLA_OK ? rc : conv3x3_fwd_plan(b, c, n, h, w, stride, out);
+}
+
+int mrla_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom_part, int b, int c, int n, int h, int w, int stride,
+                     int dtype, void* stream) {
+  if (!x || !wt || !y) return MRLA_EINVAL;
+  // a lane moves 16 bytes of x and wt, 8 of y and a 16-byte record
+  if (((uintptr_t)x | (uintptr_t)wt | (uintptr_t)y | (uintptr_t)mom_part) & 15) return MRLA_EINVAL;
+  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  if (rc != MRLA_OK) return rc;
+  return launch_conv3x3_fwd(x, wt, y, mom_part, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
+}
+
 // The stem's 7x7 / stride 2 weight gradient (stem_wgrad.hip).  One argument check for the two queries and the launch, as above.
 static int stem_conv_wgrad_args(int b, int n, int h, int w, int dtype) {
   if (b <= 0 || n <= 0 || h <= 0 || w <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;

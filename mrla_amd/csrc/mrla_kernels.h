@@ -231,6 +231,13 @@ int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
                          int s, int dtype, hipStream_t st);
+// conv3x3_fwd.hip -- the forward of that convolution as an implicit GEMM (bf16 or fp16), y [b,ho,wo,n] from x [b,h,w,c] and
+// wt [n,3,3,c], with the optional moment records mom [rows][n][MRLA_GEMM_MOMENTS] of the rounded outputs; on the flipped,
+// transposed weight at stride 1 it is the input gradient
+int conv3x3_fwd_rows(int b, int c, int n, int h, int w, int s);
+int conv3x3_fwd_plan(int b, int c, int n, int h, int w, int s, int* out);
+int launch_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom, int b, int c, int n, int h, int w, int s, int dtype,
+                       hipStream_t st);
 // stem_wgrad.hip -- the weight gradient of the stem's 7x7 / stride 2 / padding 3 convolution of three channels, dW [n,7,7,3],
 // as one product of dY^T and the pixels' seven 21-element windows (bf16 or fp16); part [rows][n][7][7][3]
 int stem_conv_wgrad_rows(int b, int n, int h, int w);

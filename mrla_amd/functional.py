@@ -108,6 +108,28 @@ def conv3x3_wgrad(enabled=True):
         CONV3X3_WGRAD = prev
 
 
+CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_applies: the bottleneck's conv2, both of the basic
+#                       block's; inference and frozen stages included) comes from mrla_conv3x3_fwd -- one fixed summation order,
+#                       no split of the reduction: a function of its inputs alone, where the stock operator's output differs
+#                       from run to run -- and so does its input gradient at stride 1 (the same kernel on the flipped,
+#                       transposed weight); in front of a train-mode BatchNorm the kernel hands over the moment records and
+#                       the separate moments pass over its output is gone (conv3x3_bn_act).  The stride-2 input gradient
+#                       stays the stock operator's.  False (the default): the very same autograd graph and launches as before;
+#                       conv3x3_fwd() turns it on for a block of code.  profiles/conv3x3_fwd.md has the numbers a change of
+#                       the default rests on.
+
+
+@contextlib.contextmanager
+def conv3x3_fwd(enabled=True):
+    """CONV3X3_FWD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
+    global CONV3X3_FWD
+    prev, CONV3X3_FWD = CONV3X3_FWD, bool(enabled)
+    try:
+        yield
+    finally:
+        CONV3X3_FWD = prev
+
+
 STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolution of three channels (stem_conv_applies: conv1 of
 #                      ResNet_mrlal) comes from mrla_stem_conv_wgrad -- fixed split, fixed summation order, no atomics --
 #                      written straight as the fp32 master weight's gradient.  The forward stays the stock operator's; the
@@ -2122,15 +2144,125 @@ class _Conv3x3Fn(torch.autograd.Function):
         return gx, gw, None
 
 
+def conv3x3_fwd_applies(conv, x):
+    """True when `conv(x)` itself belongs on mrla_conv3x3_fwd: the module, layout, dtype and shape conditions of
+    conv3x3_applies (a bias-free nn.Conv2d 3x3 / padding 1 / dilation 1 / groups 1 / stride (1, 1) or (2, 2), a CUDA
+    channels_last 16-byte-aligned input computed in bf16 or fp16, a shape the kernel takes: mrla_conv3x3_fwd_rows) -- but
+    neither grad mode nor a weight that wants its gradient: inference and frozen stages qualify."""
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride in ((1, 1), (2, 2))
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+            and conv.padding_mode == "zeros"):
+        return False
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
+        return False
+    wt = conv.weight
+    if not (wt.is_cuda and x.shape[1] == conv.in_channels):
+        return False
+    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
+    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
+        return False
+    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+        return False
+    b, c, h, w = x.shape
+    return L.load().mrla_conv3x3_fwd_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
+
+
+class _Conv3x3FwdFn(torch.autograd.Function):
+    """(y, records) = mrla_conv3x3_fwd of a channels_last bf16 or fp16 `x` on `w` cast to x's dtype as autocast casts it and
+    laid out [n, 3, 3, c]; records: the [rows, n, MRLA_GEMM_MOMENTS] moment records of y for the BatchNorm behind it where
+    `moments`, else empty.  Backward: dX at stride 1 from the same entry point on dy and the flipped, transposed weight (a
+    pure permutation), at stride 2 from the stock operator's backward; dW from mrla_conv3x3_wgrad where `own_wgrad`
+    (CONV3X3_WGRAD and conv3x3_applies at the call), else from the stock backward -- each masked to what is asked for."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, x, w, stride, moments, own_wgrad):
+        ctx.set_materialize_grads(False)
+        ctx.stride, ctx.own_wgrad = (stride, stride), own_wgrad
+        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
+        w16 = (w if w.dtype == x.dtype else w.to(x.dtype)).contiguous(memory_format=_CL)
+        if w16.data_ptr() % 16:
+            w16 = w16.clone(memory_format=_CL)
+        b, c, h, wd = x.shape
+        n, dt = w16.shape[0], _DT[x.dtype]
+        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        y = torch.empty((b, n, ho, wo), dtype=x.dtype, device=x.device, memory_format=_CL)
+        if moments:
+            rows = L.load().mrla_conv3x3_fwd_rows(b, c, n, h, wd, stride, dt)
+            part = torch.empty((max(rows, 0), n, L.GEMM_MOMENTS), dtype=torch.float32, device=x.device)
+        else:
+            part = torch.empty((0,), dtype=torch.float32, device=x.device)
+        _call("mrla_conv3x3_fwd", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w16), _ptr(y),
+              _ptr(part) if moments else None, b, c, n, h, wd, stride, dt, _stream())
+        ctx.save_for_backward(x, w16)
+        ctx.mark_non_differentiable(part)
+        return y, part
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, dy, _dpart=None):
+        if dy is None:
+            return None, None, None, None, None
+        x, w16 = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dy = dy.contiguous(memory_format=_CL)
+        b, c, h, wd = x.shape
+        n, dt = w16.shape[0], _DT[x.dtype]
+        own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
+        gx = gw = None
+        if need_w and own and ctx.own_wgrad:
+            rows = L.load().mrla_conv3x3_wgrad_rows(b, c, n, h, wd, ctx.stride[0], dt)
+            if rows > 0:
+                part = torch.empty((rows, n, 9, c), dtype=torch.float32, device=x.device)
+                gw = torch.empty((n, c, 3, 3), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
+                _call("mrla_conv3x3_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
+                      b, c, n, h, wd, ctx.stride[0], dt, _DT[ctx.wdtype], _stream())
+                need_w = False
+        if need_x and own and ctx.stride[0] == 1:
+            wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
+            gx = torch.empty_like(x)
+            _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
+                  b, n, c, h, wd, 1, dt, _stream())
+            need_x = False
+        if need_x or need_w:
+            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1,
+                                                              [need_x, need_w, False])
+            gx = gx2 if need_x else gx
+            gw = gw2.to(ctx.wdtype) if need_w else gw
+        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
+            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
+        return gx, gw, None, None, None
+
+
+def _conv3x3_own(x, conv, moments):
+    dt = _conv3x3_dtype(x)
+    return _Conv3x3FwdFn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], moments,
+                               CONV3X3_WGRAD and conv3x3_applies(conv, x))
+
+
 def conv3x3(x, conv):
     """conv(x) for the 3x3 convolutions of the blocks (resnet_mrla_light.py: conv2 of the bottleneck, both of the basic
-    block).  With CONV3X3_WGRAD off, or where conv3x3_applies says no, it IS conv(x): the same autograd graph as before.
+    block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, with
+    CONV3X3_WGRAD off, or where conv3x3_applies says no, it IS conv(x): the same autograd graph as before.
     Otherwise one autograd node whose forward and input gradient are the stock operator's and whose weight gradient is
     mrla_conv3x3_wgrad's."""
+    if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
+        return _conv3x3_own(x, conv, False)[0]
     if not (CONV3X3_WGRAD and conv3x3_applies(conv, x)):
         return conv(x)
     dt = _conv3x3_dtype(x)
     return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0])
+
+
+def conv3x3_bn_act(x, conv, bn, relu, defer=False):
+    """bn_act(conv3x3(x, conv), bn, relu, defer) -- and exactly that graph with CONV3X3_FWD off or where conv3x3_fwd_applies says
+    no.  With the own forward in front of a train-mode BatchNorm2d that bn_act fuses, the convolution also returns the moment
+    records of its output and bn_act takes them as `pre_moments` (the path the 1x1 GEMMs feed): no moments pass reads y back."""
+    if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
+        moments = type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats and bn.training
+        y, part = _conv3x3_own(x, conv, moments)
+        return bn_act(y, bn, relu, defer, pre_moments=part if moments else None)
+    return bn_act(conv3x3(x, conv), bn, relu, defer)
 
 
 def stem_conv_applies(conv, x):

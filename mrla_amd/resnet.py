@@ -90,7 +90,7 @@ class _BottleneckTrunk(nn.Module):
         # (bf16 only: in fp16 shortcut_subsample() declines and the downsample subsamples for itself.)
         sub = F_.shortcut_subsample(self.downsample, x)
         out, identity = F_.conv_bn_act(x, self.conv1, self.bn1, relu=True, passthrough=True, subsample=sub)
-        out = F_.bn_act(F_.conv3x3(out, self.conv2), self.bn2, relu=True)
+        out = F_.conv3x3_bn_act(out, self.conv2, self.bn2, relu=True)
         if self.se is not None or self.eca is not None:
             # channel attention reads bn3's output, so nothing is deferred: bn3 and the gate are one node (F_.bn_gate)
             out = F_.conv_bn_gate(out, self.conv3, self.bn3, self.se, self.eca)
@@ -165,13 +165,13 @@ class MRLA_BasicBlock(nn.Module):
 
     def forward(self, x):
         identity = x
-        out = F_.bn_act(F_.conv3x3(x, self.conv1), self.bn1, relu=True)
+        out = F_.conv3x3_bn_act(x, self.conv1, self.bn1, relu=True)
         # bn2's affine, the shortcut add and the ReLU all run inside the first MRLA pass (as bn3's do in the bottleneck)
         defer = layers.light_tail_is_fused(self.bn_mrla) and self.se is None and self.eca is None
         if self.se is not None or self.eca is not None:      # bn2 and the gate are one node
             out = F_.bn_gate(F_.conv3x3(out, self.conv2), self.bn2, self.se, self.eca)
         else:
-            out = F_.bn_act(F_.conv3x3(out, self.conv2), self.bn2, relu=False, defer=defer)
+            out = F_.conv3x3_bn_act(out, self.conv2, self.bn2, relu=False, defer=defer)
         if self.downsample is not None:
             ds = self.downsample
             if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d):
