@@ -199,27 +199,28 @@ def conv1x1_wgrad_plan(m, k, n, dtype=None):
     return tuple(out) if rc == OK else None
 
 
+def _spatial_plan(entry, count, shape, dtype):
+    """The `count` integers `entry` answers for the integers `shape` and the dtype (bf16 if None), or None."""
+    out = (ctypes.c_int * count)()
+    rc = getattr(load(), entry)(*shape, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
 def conv3x3_wgrad_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_wgrad, or None."""
-    out = (ctypes.c_int * 6)()
-    rc = load().mrla_conv3x3_wgrad_plan(b, c, n, h, w, stride, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _spatial_plan("mrla_conv3x3_wgrad_plan", 6, (b, c, n, h, w, stride), dtype)
 
 
 def conv3x3_fwd_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, output rows per workgroup, rows per step, segments per row, record rows, workgroups) of mrla_conv3x3_fwd, or
     None."""
-    out = (ctypes.c_int * 6)()
-    rc = load().mrla_conv3x3_fwd_plan(b, c, n, h, w, stride, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _spatial_plan("mrla_conv3x3_fwd_plan", 6, (b, c, n, h, w, stride), dtype)
 
 
 def stem_conv_wgrad_plan(b, n, h, w, dtype=None):
     """(tile n, output rows per split, splits, column segments per row, LDS bytes, output columns per segment, output rows
     per step) of mrla_stem_conv_wgrad, or None."""
-    out = (ctypes.c_int * 7)()
-    rc = load().mrla_stem_conv_wgrad_plan(b, n, h, w, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _spatial_plan("mrla_stem_conv_wgrad_plan", 7, (b, n, h, w), dtype)
 
 
 def bn_pool_plan(b, c, h, w, dtype, band=0):

@@ -756,47 +756,54 @@ int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
-// The 3x3 weight gradient (conv3x3_wgrad.hip).  One argument check for the two queries and the launch, so that the three
-// answer the same code for the same arguments.
-static int conv3x3_wgrad_args(int b, int c, int n, int h, int w, int stride, int dtype) {
+// The spatial convolutions (conv3x3_wgrad.hip, conv3x3_fwd.hip, stem_wgrad.hip).  One argument check for the queries and the
+// launches of a shape, so that they answer the same code for the same arguments.
+static int conv3x3_args(int b, int c, int n, int h, int w, int stride, int dtype) {
   if (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || stride <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return MRLA_OK;
 }
 
+static int stem_conv_wgrad_args(int b, int n, int h, int w, int dtype) { return conv3x3_args(b, 3, n, h, w, 2, dtype); }
+
+// What a weight-gradient launch checks on top of its shape's code `rc`, in the order the codes are documented in: a lane
+// moves 16 bytes (aligned dwords) of dy, x and part, and four elements of dw; dw is of the operands' type or fp32 -- a 16-bit
+// dw_dtype other than dtype is a caller's mistake (as mrla_conv1x1_wgrad), also where the shape is unsupported.
+static int wgrad_launch_args(const void* dy, const void* x, const void* part, const void* dw, int dtype, int dw_dtype, int rc) {
+  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  if (rc == MRLA_EINVAL) return rc;
+  if (dw_dtype != MRLA_F32 && dw_dtype != dtype) return MRLA_EINVAL;
+  return rc;
+}
+
 int mrla_conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int stride, int dtype) {
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   return rc != MRLA_OK ? rc : conv3x3_wgrad_rows(b, c, n, h, w, stride);
 }
 
 int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out) {
   if (!out) return MRLA_EINVAL;
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   return rc != MRLA_OK ? rc : conv3x3_wgrad_plan(b, c, n, h, w, stride, out);
 }
 
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w, int stride,
                        int dtype, int dw_dtype, void* stream) {
-  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
-  // a lane moves 16 bytes of dy, x and part, and four elements of dw
-  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
-  if (rc == MRLA_EINVAL) return rc;
-  if (dw_dtype != MRLA_F32 && dw_dtype != dtype) return MRLA_EINVAL;      // (as mrla_conv1x1_wgrad: a caller's mistake)
+  const int rc = wgrad_launch_args(dy, x, part, dw, dtype, dw_dtype, conv3x3_args(b, c, n, h, w, stride, dtype));
   if (rc != MRLA_OK) return rc;
   return launch_conv3x3_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
 }
 
-// The 3x3 forward (conv3x3_fwd.hip).  The argument check is the weight gradient's: one code from the queries and the launch.
 int mrla_conv3x3_fwd_rows(int b, int c, int n, int h, int w, int stride, int dtype) {
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   return rc != MRLA_OK ? rc : conv3x3_fwd_rows(b, c, n, h, w, stride);
 }
 
 int mrla_conv3x3_fwd_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out) {
   if (!out) return MRLA_EINVAL;
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   return rc != MRLA_OK ? rc : conv3x3_fwd_plan(b, c, n, h, w, stride, out);
 }
 
@@ -805,16 +812,9 @@ int mrla_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom_part, in
   if (!x || !wt || !y) return MRLA_EINVAL;
   // a lane moves 16 bytes of x and wt, 8 of y and a 16-byte record
   if (((uintptr_t)x | (uintptr_t)wt | (uintptr_t)y | (uintptr_t)mom_part) & 15) return MRLA_EINVAL;
-  const int rc = conv3x3_wgrad_args(b, c, n, h, w, stride, dtype);
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   if (rc != MRLA_OK) return rc;
   return launch_conv3x3_fwd(x, wt, y, mom_part, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
-}
-
-// The stem's 7x7 / stride 2 weight gradient (stem_wgrad.hip).  One argument check for the two queries and the launch, as above.
-static int stem_conv_wgrad_args(int b, int n, int h, int w, int dtype) {
-  if (b <= 0 || n <= 0 || h <= 0 || w <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return MRLA_OK;
 }
 
 int mrla_stem_conv_wgrad_rows(int b, int n, int h, int w, int dtype) {
@@ -830,13 +830,7 @@ int mrla_stem_conv_wgrad_plan(int b, int n, int h, int w, int dtype, int* out) {
 
 int mrla_stem_conv_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int n, int h, int w, int dtype,
                          int dw_dtype, void* stream) {
-  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
-  // a lane moves 16 bytes of dy and part, aligned dwords of x, and four elements of dw
-  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  const int rc = stem_conv_wgrad_args(b, n, h, w, dtype);
-  if (rc == MRLA_EINVAL) return rc;
-  if (dw_dtype != MRLA_F32 && dw_dtype != dtype) return MRLA_EINVAL;
+  const int rc = wgrad_launch_args(dy, x, part, dw, dtype, dw_dtype, stem_conv_wgrad_args(b, n, h, w, dtype));
   if (rc != MRLA_OK) return rc;
   return launch_stem_conv_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, b, n, h, w, dtype, (hipStream_t)stream);
 }

@@ -5,19 +5,15 @@
 // the basic block, which the reference leaves to cuDNN; with the weight flipped and transposed (wflip[c, kh, kw, n] =
 // wt[n, 2-kh, 2-kw, c]) the same kernel at stride 1 is that convolution's input gradient.
 //
-// Ownership: a workgroup owns 64 output channels and a FIXED range of output rows (a row = one image row of y; rows are
-// numbered image after image, as in conv3x3_wgrad.hip).  It walks its range in steps of R rows of ONE image -- or, for rows
-// wider than a step, pieces of one row -- and for every step sums all nine taps and all of c, in c-chunks of 64 in ascending
-// order, in fp32 accumulators: no split over the reduction, no atomics, no memset, every element of y written exactly once,
+// Ownership (conv_spatial.h): a workgroup owns 64 output channels and a FIXED range of output rows.  It walks its range in
+// steps of R rows of ONE image -- or, for rows wider than a step, pieces of one row -- and for every step sums all nine
+// taps and all of c, in c-chunks of 64 in ascending order, in fp32 accumulators: no split over the reduction, no atomics, no memset, every element of y written exactly once,
 // one rounding to nearest even at the store.  y and the records are a function of the arguments alone.
 //
-// Borders: conv3x3_wgrad.hip's X raster.  Output pixel (ry, j) of a step is accumulator column p = ry*PY + j; X pixel
-// (ty, cx) -- input row yo0*s - 1 + ty, input column xo0*s - 1 + cx -- sits at LDS row ty*PX + cx with PX = s*PY, so tap
-// (kh, kw) of column p reads row s*p + s*(s-1)*PY*ry + kh*PX + kw: a constant offset from a row the lane computes once per
-// step.  Everything in the raster that is no pixel of this image is written as zeros by the loader (rows above the first and
-// below the last row of the image are NOT the neighbouring image's), whose every global load is predicated on its own
-// pixel's coordinates: nothing is read outside x or wt.  The pad columns and the tail of the raster are computed and not
-// stored (81/49 of the useful MFMA work at a 7x7 map).
+// Borders: conv_spatial.h's X raster.  Output pixel (ry, j) of a step is accumulator column p = ry*PY + j,
+// so tap (kh, kw) of column p reads raster row s*p + s*(s-1)*PY*ry + kh*PX + kw: a constant offset from a row the lane
+// computes once per step.  Nothing is read outside x or wt.  The pad columns and the tail of the raster are computed and
+// not stored (81/49 of the useful MFMA work at a 7x7 map).
 //
 // Operands: both are contiguous along c.  The weights of the c-chunk sit in LDS as [64 n][9 taps][64 c] (72 KB; loaded
 // once per workgroup where c = 64, per step and chunk otherwise), the raster as [pixel][64 c]; rows are 128 bytes and 16-byte
@@ -34,9 +30,7 @@
 // butterfly and the two pixel-waves in ascending order: a fixed order.
 #include <algorithm>
 
-#include "conv1x1_elem.h"
-#include "mrla_device.h"
-#include "mrla_kernels.h"
+#include "conv_spatial.h"
 
 namespace mrla {
 namespace {
@@ -48,15 +42,10 @@ constexpr int kF3Target = 256;          // workgroups: one per CU
 constexpr int kF3MaxKP1 = 128;          // raster pixels (accumulator columns) of a step at stride 1: four 32-pixel blocks
 constexpr int kF3MaxKP2 = 96;           // ... at stride 2, where the X raster has four times the rows (<= 62 KB)
 constexpr int kF3MaxPY = 60;            // raster pitch of the outputs
-constexpr int kF3RowB = 128;            // bytes of an LDS row: 64 channels of one pixel / of one (n, tap)
 constexpr int kF3WRows = kF3Tile * 9;   // weight rows of a c-chunk
 constexpr int kF3Misc = 2048;           // pivots [64] and the two pixel-waves' sums [2][64][2], in front of the tiles
 
-struct F3Plan {
-  int ok = 0;
-  int ho = 0, wo = 0;
-  int py = 0, ws = 0, nseg = 0, rmax = 0;      // raster pitch, output columns per segment, segments per row, rows per step
-  int xt_cap = 0;                              // rows of the X raster
+struct F3Plan : Raster3x3 {
   int rows_per_wg = 0, ranges = 0, tiles = 0;
 };
 
@@ -67,7 +56,7 @@ struct F3Args {
   float inv_py, inv_px;
 };
 
-__device__ __forceinline__ int f3_off(int row, int chunk) { return row * kF3RowB + ((chunk ^ ((row >> 1) & 7)) << 4); }
+__device__ __forceinline__ int f3_off(int row, int chunk) { return tile_off<7, 0>(row, chunk); }
 
 // grid: (n / 64) * ranges workgroups, 256 threads; LDS = kF3Misc + (576 + xt_cap) * 128 bytes
 template <typename T, int S, bool MOM>
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_fwd_kernel(const T* __res
   float* const s_piv = reinterpret_cast<float*>(smem_raw);
   float* const s_red = s_piv + kF3Tile;
   unsigned char* const w_tile = smem_raw + kF3Misc;
-  unsigned char* const x_tile = w_tile + kF3WRows * kF3RowB;
+  unsigned char* const x_tile = w_tile + kF3WRows * kTileRowB;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int tiles_n = a.n / kF3Tile;
   const int range = blockIdx.x / tiles_n, n0 = (blockIdx.x - range * tiles_n) * kF3Tile;
@@ -99,8 +88,8 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_fwd_kernel(const T* __res
   bool first = true;
 
   for (int r = r_begin; r < r_end;) {
-    const int img = r / a.ho, yo0 = r - img * a.ho;
-    const int R = min(a.rmax, min(a.ho - yo0, r_end - r));
+    const RowStep st = row_step(r, r_end, a.ho, a.rmax);
+    const int img = st.img, yo0 = st.yo0, R = st.R;
     for (int seg = 0; seg < a.nseg; ++seg) {
       const int xo0 = seg * a.ws, ws = min(a.ws, a.wo - xo0);
       const int KP = (R * PY + 31) & ~31;
@@ -255,35 +244,19 @@ __global__ __launch_bounds__(kThreads, 1) void conv3x3_fwd_kernel(const T* __res
 #endif
 }
 
-size_t f3_lds_bytes(const F3Plan& p) { return kF3Misc + (size_t)(kF3WRows + p.xt_cap) * kF3RowB; }
+size_t f3_lds_bytes(const F3Plan& p) { return kF3Misc + (size_t)(kF3WRows + p.xt_cap) * kTileRowB; }
 
-// The raster of a step as in conv3x3_wgrad.hip: whole output rows where one fits (pitch = the row + its pads), else pieces of
-// one row; as many rows as kF3MaxKP1 / kF3MaxKP2 accumulator columns hold.  Ranges of output rows so that the grid is one
-// workgroup per CU.
+// conv_spatial.h's raster of a step (accumulator columns in whole 32-pixel blocks), and ranges of output rows so that the
+// grid is one workgroup per CU.
 F3Plan f3_plan(int b, int c, int n, int h, int w, int s) {
   F3Plan p;
-  if (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || (s != 1 && s != 2) || c % kF3Tile || n % kF3Tile) return p;
-  if ((unsigned long long)b * h * w * std::max(c, n) * 2 >= 1ull << 31) return p;
-  p.ho = (h - 1) / s + 1;
-  p.wo = (w - 1) / s + 1;
-  const int pad = s == 1 ? 2 : 1;                          // s*PY >= the X columns of a segment, s*(ws - 1) + 3
-  if (p.wo + pad <= kF3MaxPY) {
-    p.ws = p.wo; p.py = p.wo + pad; p.nseg = 1;
-    p.rmax = std::max(1, std::min(p.ho, (s == 1 ? kF3MaxKP1 : kF3MaxKP2) / p.py));
-  } else {
-    p.py = kF3MaxPY; p.ws = kF3MaxPY - pad; p.nseg = (p.wo + p.ws - 1) / p.ws;
-    p.rmax = 1;
-  }
-  const int kp_cap = (p.rmax * p.py + 31) & ~31;
-  p.xt_cap = (s * kp_cap + s * (s - 1) * p.py * (p.rmax - 1) + 2 * s * p.py + 3 + 7) & ~7;
+  static_cast<Raster3x3&>(p) = raster3x3(b, c, n, h, w, s, kF3MaxKP1, kF3MaxKP2, kF3MaxPY, 32);
+  if (!p.ok) return p;
   p.tiles = n / kF3Tile;
-  const long long rows = (long long)b * p.ho;
   // where c = 64 the weights (72 KB, three times a step's raster) are loaded once per workgroup: at least two full steps behind them
-  const long long floor_rows = (c == kF3Tile ? 2 : 1) * p.rmax;
-  const long long want =
-      std::max<long long>(1, std::min<long long>(rows / floor_rows, (kF3Target + p.tiles - 1) / p.tiles));
-  p.rows_per_wg = (int)((rows + want - 1) / want);
-  p.ranges = (int)((rows + p.rows_per_wg - 1) / p.rows_per_wg);
+  const RowSplit sp = split_rows((long long)b * p.ho, p.tiles, kF3Target, (c == kF3Tile ? 2 : 1) * p.rmax);
+  p.rows_per_wg = sp.per;
+  p.ranges = sp.count;
   // (weights + raster <= 136 KB by the caps above; the queries and the launch answer from this one place)
   p.ok = f3_lds_bytes(p) <= 160 * 1024;
   return p;

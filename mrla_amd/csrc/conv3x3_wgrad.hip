@@ -11,15 +11,11 @@
 // tile to part[split][n][9][c] and a second kernel sums the splits in ascending order.  No atomics, no memset; every element
 // of part and dw is written exactly once per call, and the result is a function of the inputs and the shape alone.
 //
-// Borders without per-lane masks: a step takes R output rows of ONE image (or, for rows wider than a step, a piece of one
-// row) and keeps both operands in LDS as padded rasters.  dY pixel (ry, j) sits at tile row ry*PY + j, X pixel (ty, cx) --
-// input row yo0*s - 1 + ty, input column xo0*s - 1 + cx -- at tile row ty*PX + cx with PX = s*PY, so the X pixel that tap
-// (kh, kw) pairs with dY tile row p = ry*PY + j is X tile row (s*ry + kh)*PX + s*j + kw = s*p + s*(s-1)*PY*ry + kh*PX + kw:
-// a tap is a constant offset from a row the lane computes once per k-step (s*p itself at stride 1).  Everything in the
-// rasters that is no pixel of this step -- the pad columns of dY, X pixels outside the image, rows above the first and below the last row
-// of the image (NOT the neighbouring image's rows), the tail up to a multiple of 16 pixels -- is written as zeros by the
-// loader, whose every global load is predicated on the pixel's own coordinates: nothing is read outside x or dy.  The pad
-// pixels of dY multiply into nothing (9/7 of the MFMA work at a 7x7 map).
+// Borders without per-lane masks: conv_spatial.h's rasters.  A step keeps both operands in LDS as padded rasters, dY pixel
+// (ry, j) at tile row ry*PY + j and X pixel (ty, cx) at tile row ty*PX + cx, so a tap is a constant offset from a row the lane
+// computes once per k-step.  The pad columns of dY and its tail up to a multiple of 16 pixels are written as zeros by a loader
+// predicated like the X raster's: nothing is read outside x or dy.  The pad pixels of dY multiply into nothing (9/7 of the
+// MFMA work at a 7x7 map).
 //
 // The loader is register-staged (16-byte pieces, four in flight per lane) and synchronous; two workgroups per CU
 // (__launch_bounds__(256, 2), <= 80 KB of LDS each) overlap one's loads with the other's MFMAs.  Both MFMA operands are COLUMNS
@@ -32,16 +28,12 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "conv1x1_elem.h"
-#include "mrla_device.h"
-#include "mrla_kernels.h"
+#include "conv_spatial.h"
 
 namespace mrla {
 namespace {
 
-typedef short c3_s16x4 __attribute__((ext_vector_type(4)));
 typedef c1_f32x16 c3_f32x16;
-typedef __attribute__((address_space(3))) c3_s16x4* c3_lds_s16x4_ptr;
 
 constexpr int kC3Tile = 64;             // output tile: 64 n x 64 c (x 9 taps)
 constexpr int kC3Waves = 4;             // 2 x 2 waves, a 32 x 32 block of each tap per wave
@@ -51,13 +43,9 @@ constexpr int kC3MaxKP1 = 128;          // dY raster rows of a step at stride 1:
 constexpr int kC3MaxKP2 = 96;           // ... at stride 2, where the X raster has four times the pixels: (96 + 4*96 + 2*48 + 3 + 7)
                                         // * 128 B = 74 KB at most (c3_plan's xt_cap with py * rmax <= 96, py <= 48 where rmax >= 2)
 constexpr int kC3MaxPY = 60;            // dY raster pitch
-constexpr int kC3RowB = kC3Tile * 2;    // bytes of a tile row (one pixel, 64 channels)
+static_assert(kTileRowB == kC3Tile * 2, "a tile row is one pixel, 64 channels");
 
-struct C3Plan {
-  int ok = 0;
-  int ho = 0, wo = 0;
-  int py = 0, ws = 0, nseg = 0, rmax = 0;      // raster pitch, output columns per segment, segments per row, rows per step
-  int kp_cap = 0, xt_cap = 0;                  // tile rows of the two rasters
+struct C3Plan : Raster3x3 {
   int rows_per_split = 0, splits = 0, tiles = 0;
 };
 
@@ -68,16 +56,13 @@ struct C3Args {
   float inv_py, inv_px;
 };
 
-__device__ __forceinline__ int c3_swz(int row) { return ((row >> 1) & 1) << 2; }
-__device__ __forceinline__ int c3_off(int row, int chunk) { return row * kC3RowB + ((chunk ^ c3_swz(row)) << 4); }
+__device__ __forceinline__ int c3_off(int row, int chunk) { return tile_off<1, 2>(row, chunk); }
 
 // 32x32x16 operand: this lane's 4 channels (of the 16-lane group's 16) of tile rows r and r2, its pixel of the k-step's first
 // and second eight
 template <typename T>
 __device__ __forceinline__ typename Elem16<T>::x8 c3_frag(const unsigned char* tile, int r, int r2, int chunk, int sub) {
-  const c3_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((c3_lds_s16x4_ptr)(tile + c3_off(r, chunk) + sub));
-  const c3_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((c3_lds_s16x4_ptr)(tile + c3_off(r2, chunk) + sub));
-  return __builtin_bit_cast(typename Elem16<T>::x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  return tr16_frag<T>(tile + c3_off(r, chunk) + sub, tile + c3_off(r2, chunk) + sub);
 }
 
 // grid: tiles * splits workgroups, 256 threads; LDS = (kp_cap + xt_cap) * 128 bytes
@@ -87,7 +72,7 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   unsigned char* const ty_tile = smem_raw;
-  unsigned char* const tx_tile = smem_raw + a.kp_cap * kC3RowB;
+  unsigned char* const tx_tile = smem_raw + a.kp_cap * kTileRowB;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int tiles = (a.n / kC3Tile) * a.tiles_c;
   const int split = blockIdx.x / tiles, tile = blockIdx.x - split * tiles;
@@ -98,6 +83,8 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
   const int PY = a.py, PX = S * a.py;
 
   const int wn = wave >> 1, wc = wave & 1;
+  // (tr_krel, tr_col, tr_chunk and tr_sub of conv_spatial.h written out: through the helpers this kernel's prologue comes out
+  // in another order)
   const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
   const int krel = 8 * (g >> 1) + q;                       // this lane's pixel of a 16-pixel k-step (and +4)
   const int colA = wn * 32 + 16 * (g & 1) + 4 * pp, colB = wc * 32 + 16 * (g & 1) + 4 * pp;
@@ -113,8 +100,8 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
 
   for (int r = r_begin; r < r_end;) {
-    const int img = r / a.ho, yo0 = r - img * a.ho;
-    const int R = min(a.rmax, min(a.ho - yo0, r_end - r));
+    const RowStep st = row_step(r, r_end, a.ho, a.rmax);
+    const int img = st.img, yo0 = st.yo0, R = st.R;
     for (int seg = 0; seg < a.nseg; ++seg) {
       const int xo0 = seg * a.ws, ws = min(a.ws, a.wo - xo0);
       const int KP = (R * PY + 15) & ~15;
@@ -197,53 +184,21 @@ __global__ __launch_bounds__(kC3Waves* kWave, 2) void conv3x3_wgrad_kernel(const
   conv3x3_wgrad_body<T, S>(dY, X, part, a);
 }
 
-// dW[e] = part[0][e] + part[1][e] + ... in ascending order of the split; a lane takes four consecutive outputs
-template <typename TO>
-__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const float* __restrict__ part, TO* __restrict__ dW,
-                                                                   int splits, int total4) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
-  const float4* src = reinterpret_cast<const float4*>(part) + i;
-  float4 s = src[0];
-#pragma unroll 8
-  for (int k = 1; k < splits; ++k) {
-    const float4 v = src[(size_t)k * total4];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  TO* o = dW + (size_t)i * 4;
-  o[0] = from_f<TO>(s.x); o[1] = from_f<TO>(s.y); o[2] = from_f<TO>(s.z); o[3] = from_f<TO>(s.w);
-}
-
-// The raster of a step: whole output rows where one fits (pitch = the row + its pads), else pieces of one row; as many rows
-// as kC3MaxKP1 / kC3MaxKP2 raster pixels hold.  Splits over output rows so that the grid is two workgroups per CU.
+// conv_spatial.h's raster of a step, and splits over output rows so that the grid is two workgroups per CU.
 C3Plan c3_plan(int b, int c, int n, int h, int w, int s) {
   C3Plan p;
-  if (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || (s != 1 && s != 2) || c % kC3Tile || n % kC3Tile) return p;
-  if ((unsigned long long)b * h * w * std::max(c, n) * 2 >= 1ull << 31) return p;
-  p.ho = (h - 1) / s + 1;
-  p.wo = (w - 1) / s + 1;
-  const int pad = s == 1 ? 2 : 1;                          // s*PY >= the X columns of a segment, s*(ws - 1) + 3
-  if (p.wo + pad <= kC3MaxPY) {
-    p.ws = p.wo; p.py = p.wo + pad; p.nseg = 1;
-    p.rmax = std::max(1, std::min(p.ho, (s == 1 ? kC3MaxKP1 : kC3MaxKP2) / p.py));
-  } else {
-    p.py = kC3MaxPY; p.ws = kC3MaxPY - pad; p.nseg = (p.wo + p.ws - 1) / p.ws;
-    p.rmax = 1;
-  }
-  p.kp_cap = (p.rmax * p.py + 15) & ~15;
-  p.xt_cap = (s * p.kp_cap + s * (s - 1) * p.py * (p.rmax - 1) + 2 * s * p.py + 3 + 7) & ~7;
+  static_cast<Raster3x3&>(p) = raster3x3(b, c, n, h, w, s, kC3MaxKP1, kC3MaxKP2, kC3MaxPY, 16);
+  if (!p.ok) return p;
   p.tiles = (n / kC3Tile) * (c / kC3Tile);
-  const long long rows = (long long)b * p.ho;
-  const long long want = std::max<long long>(1, std::min<long long>(rows, (kC3Target + p.tiles - 1) / p.tiles));
-  p.rows_per_split = (int)((rows + want - 1) / want);
-  p.splits = (int)((rows + p.rows_per_split - 1) / p.rows_per_split);
-  p.ok = 1;
+  const RowSplit sp = split_rows((long long)b * p.ho, p.tiles, kC3Target);
+  p.rows_per_split = sp.per;
+  p.splits = sp.count;
   return p;
 }
 
 template <typename T, int S>
 int c3_launch(const C3Plan& p, const C3Args& a, const void* dy, const void* x, float* part, hipStream_t st) {
-  const size_t lds = (size_t)(p.kp_cap + p.xt_cap) * kC3RowB;
+  const size_t lds = (size_t)(p.kp_cap + p.xt_cap) * kTileRowB;
   if (lds > 80 * 1024) return MRLA_EUNSUPPORTED;
   if (lds_opt_in(reinterpret_cast<const void*>(conv3x3_wgrad_kernel<T, S>), lds) != hipSuccess) return MRLA_EHIP;
   hipLaunchKernelGGL((conv3x3_wgrad_kernel<T, S>), dim3(p.tiles * p.splits), dim3(kC3Waves * kWave), lds, st, (const T*)dy,
@@ -281,15 +236,7 @@ int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, i
   else
     rc = s == 1 ? c3_launch<bf16_t, 1>(p, a, dy, x, part, st) : c3_launch<bf16_t, 2>(p, a, dy, x, part, st);
   if (rc != MRLA_OK) return rc;
-  const int total4 = n * 9 * c / 4;
-  const dim3 grid((total4 + 255) / 256), block(256);
-  if (dw_f32)      // the fp32 master weight's gradient directly
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<float>, grid, block, 0, st, part, (float*)dw, p.splits, total4);
-  else if (dtype == MRLA_F16)
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<f16_t>, grid, block, 0, st, part, (f16_t*)dw, p.splits, total4);
-  else
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel<bf16_t>, grid, block, 0, st, part, (bf16_t*)dw, p.splits, total4);
-  return hip_status(hipGetLastError());
+  return launch_split_sum(part, dw, dw_f32, dtype, p.splits, n * 9 * c, st);
 }
 
 }  // namespace mrla

@@ -4,12 +4,11 @@
 // Reference: the backward of conv1 of resnet/models/resnet_mrla_light.py (nn.Conv2d(3, 64, 7, 2, 3, bias=False)), which the
 // reference leaves to cuDNN; the stock library's solver for it accumulates with atomics.
 //
-// The contract is conv3x3_wgrad.hip's:
+// The contract is conv_spatial.h's:
 //   * No atomics and no memset.  A workgroup owns one output tile (64 n x all 147 (kh, kw, c)) and a FIXED range of output
-//     rows (a row = one image row of dY; rows are numbered image after image); it writes its fp32 partial tile to
-//     part[split][n][7][7][3] and a second kernel sums the splits in ascending order into dw (fp32, or the operands' 16-bit
-//     type rounded once).  Every element of part and dw is written exactly once per call; the result depends on the
-//     arguments and the shape only.
+//     rows; it writes its fp32 partial tile to part[split][n][7][7][3] and split_sum_kernel sums the splits in ascending
+//     order into dw (fp32, or the operands' 16-bit type rounded once).  Every element of part and dw is written exactly once
+//     per call; the result depends on the arguments and the shape only.
 //   * Every global load is predicated on its own pixel's coordinates: nothing is read outside x or dy, and a step never
 //     reads the neighbouring image's rows as if they were padding (rows above the first and below the last row of the image
 //     are written to LDS as zeros).
@@ -18,7 +17,7 @@
 // Geometry.  In NHWC with c = 3 the 7 x 3 = 21 values that tap row kh pairs with output pixel (y, x) are contiguous:
 // elements 6x - 9 .. 6x + 11 of input row 2y + kh - 3.  A step takes R output rows of ONE image (or, for rows wider than
 // kSwMaxWS output pixels, a column segment of one row) and stages
-//   * the dY pixels as a pixel-major tile [p = ry * ws + xl][64 n] (128-byte rows, conv3x3_wgrad.hip's swizzle), zeros from
+//   * the dY pixels as a pixel-major tile [p = ry * ws + xl][64 n] (128-byte rows, tile_off<1, 2>), zeros from
 //     R * ws up to a multiple of 16, and
 //   * the 2R + 5 input rows 2*yo0 - 3 + t as rows of 16-bit elements e = 0 .. 6*ws + 17, e being element 6*xo0 - 9 + e of
 //     the input row: nine zeros in front of and behind the image's row, zero rows outside the image.
@@ -40,18 +39,13 @@
 //
 // Supported: b, h, w >= 1, n % 64 == 0, bf16 or fp16, b*h*w*max(3, n)*2 < 2^31 (32-bit element offsets).
 #include <algorithm>
-#include <type_traits>
 
-#include "conv1x1_elem.h"
-#include "mrla_device.h"
-#include "mrla_kernels.h"
+#include "conv_spatial.h"
 
 namespace mrla {
 namespace {
 
-typedef short sw_s16x4 __attribute__((ext_vector_type(4)));
 typedef c1_f32x16 sw_f32x16;
-typedef __attribute__((address_space(3))) sw_s16x4* sw_lds_s16x4_ptr;
 
 constexpr int kSwTile = 64;             // output tile: 64 n x (7 x 24 -> 192) columns
 constexpr int kSwWaves = 4;             // 2 (n) x 2 (column halves); three 32 x 32 blocks per wave
@@ -62,7 +56,7 @@ constexpr int kSwMaxWS = 128;           // output columns of a step
 constexpr int kSwMaxKP = 256;           // dY pixels of a step (32 KB): eight 16-byte pieces a lane, all in flight at once
 constexpr int kSwMaxR = 16;             // output rows of a step (bounds the X raster of narrow maps)
 static_assert(kSwMaxKP == 8 * 32 && kSwMaxWS <= kSwMaxKP, "the dY loader takes the tile in one pass");
-constexpr int kSwRowB = kSwTile * 2;   // bytes of a dY tile row (one pixel, 64 channels)
+static_assert(kTileRowB == kSwTile * 2, "a dY tile row is one pixel, 64 channels");
 constexpr int kSwLdsCap = 64 * 1024;    // LDS of a workgroup, at most (ws = 128, R = 2: 32 KB + 9 * 3200 B)
 
 struct SwPlan {
@@ -80,16 +74,7 @@ struct SwArgs {
   float inv_ws, inv_runs;
 };
 
-__device__ __forceinline__ int sw_swz(int row) { return ((row >> 1) & 1) << 2; }
-__device__ __forceinline__ int sw_off(int row, int chunk) { return row * kSwRowB + ((chunk ^ sw_swz(row)) << 4); }
-
-__device__ __forceinline__ sw_s16x4 sw_tr(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((sw_lds_s16x4_ptr)p);
-}
-template <typename T>
-__device__ __forceinline__ typename Elem16<T>::x8 sw_join(sw_s16x4 lo, sw_s16x4 hi) {
-  return __builtin_bit_cast(typename Elem16<T>::x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+__device__ __forceinline__ int sw_off(int row, int chunk) { return tile_off<1, 2>(row, chunk); }
 
 // grid: (n / 64) * splits workgroups, 256 threads; LDS = kp_cap * 128 + (2 * rmax + 5) * 2 * pd * 4 bytes
 template <typename T>
@@ -98,7 +83,7 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
 #if defined(__HIP_DEVICE_COMPILE__)
   extern __shared__ __align__(16) unsigned char smem_raw[];
   unsigned char* const ty_tile = smem_raw;
-  unsigned char* const tx_rows = smem_raw + a.kp_cap * kSwRowB;
+  unsigned char* const tx_rows = smem_raw + a.kp_cap * kTileRowB;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int tiles = a.n / kSwTile;
   const int split = blockIdx.x / tiles, tn = blockIdx.x - split * tiles;
@@ -108,16 +93,15 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
   const int copyB = a.pd * 4, rowB = 2 * copyB;             // bytes of one copy / of both copies of a staged input row
 
   const int wn = wave >> 1, wc = wave & 1;
-  const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
-  const int krel = 8 * (g >> 1) + q;                        // this lane's pixel of a 16-pixel k-step (and +4)
-  const int colA = wn * 32 + 16 * (g & 1) + 4 * pp;
-  const int chA = colA >> 3, subA = ((colA >> 2) & 1) * 8;
+  const int krel = tr_krel(lane);                           // this lane's pixel of a 16-pixel k-step (and +4)
+  const int colA = tr_col(wn * 32, lane);
+  const int chA = tr_chunk(colA), subA = tr_sub(colA);
   // this lane's four columns of each of its wave's three blocks: (kh, j .. j + 3), a constant byte offset from the pixel's
   // window in staged row 2*ry (the eighth block of 24 does not exist: held at kh = 6, accumulated and never stored)
   int offB[kSwBlocks];
 #pragma unroll
   for (int bl = 0; bl < kSwBlocks; ++bl) {
-    const int col = 32 * (kSwBlocks * wc + bl) + 16 * (g & 1) + 4 * pp;
+    const int col = tr_col(32 * (kSwBlocks * wc + bl), lane);
     const int kh = min(col / 24, 6), j = col % 24;
     offB[bl] = kh * rowB + 2 * j;
   }
@@ -137,8 +121,8 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
   const unsigned short* const Xe = reinterpret_cast<const unsigned short*>(X);
 
   for (int r = r_begin; r < r_end;) {
-    const int img = r / a.ho, yo0 = r - img * a.ho;
-    const int R = min(a.rmax, min(a.ho - yo0, r_end - r));
+    const RowStep st = row_step(r, r_end, a.ho, a.rmax);
+    const int img = st.img, yo0 = st.yo0, R = st.R;
     for (int seg = 0; seg < a.nseg; ++seg) {
       const int xo0 = seg * a.ws, ws = min(a.ws, a.wo - xo0);
       // (ws < a.ws only in the ragged last segment of a row cut into segments, where R = 1: pixel p = xl under either pitch)
@@ -217,7 +201,7 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
       // ---- the product over the step's pixels ----
       for (int k0 = 0; k0 < KP; k0 += 16) {
         const int k = k0 + krel;
-        const typename Elem16<T>::x8 fa = sw_join<T>(sw_tr(ty_tile + sw_off(k, chA) + subA), sw_tr(ty_tile + sw_off(k + 4, chA) + subA));
+        const typename Elem16<T>::x8 fa = tr16_frag<T>(ty_tile + sw_off(k, chA) + subA, ty_tile + sw_off(k + 4, chA) + subA);
         // the window of pixel p = ry * ws + xl: staged row 2*ry, byte 12*xl (+ 4 in the second copy for odd xl).  The tail
         // behind the step's last pixel, all zeros in dY, reads the last pixel's window: written, finite numbers.
         const int p1 = min(k, NP - 1), p2 = min(k + 4, NP - 1);
@@ -227,7 +211,7 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
         const unsigned char* const b2 = tx_rows + 2 * ry2 * rowB + 12 * xl2 + (xl2 & 1) * (copyB + 4);
 #pragma unroll
         for (int bl = 0; bl < kSwBlocks; ++bl) {
-          const typename Elem16<T>::x8 fb = sw_join<T>(sw_tr(b1 + offB[bl]), sw_tr(b2 + offB[bl]));
+          const typename Elem16<T>::x8 fb = tr16_frag<T>(b1 + offB[bl], b2 + offB[bl]);
           Elem16<T>::mfma(acc[bl], fa, fb);
         }
       }
@@ -250,23 +234,6 @@ __global__ __launch_bounds__(kSwWaves* kWave, 2) void stem_wgrad_kernel(const T*
 #endif
 }
 
-// dW[e] = part[0][e] + part[1][e] + ... in ascending order of the split; a lane takes four consecutive outputs
-template <typename TO>
-__global__ __launch_bounds__(256) void stem_wgrad_reduce_kernel(const float* __restrict__ part, TO* __restrict__ dW, int splits,
-                                                                int total4) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total4) return;
-  const float4* src = reinterpret_cast<const float4*>(part) + i;
-  float4 s = src[0];
-#pragma unroll 8
-  for (int k = 1; k < splits; ++k) {
-    const float4 v = src[(size_t)k * total4];
-    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-  }
-  TO* o = dW + (size_t)i * 4;
-  o[0] = from_f<TO>(s.x); o[1] = from_f<TO>(s.y); o[2] = from_f<TO>(s.z); o[3] = from_f<TO>(s.w);
-}
-
 // A step: whole output rows where one has at most kSwMaxWS pixels -- as many as kSwMaxKP pixels hold, kSwMaxR at most --
 // else segments of one row.  Splits over output rows so that the grid is two workgroups per CU where the rows allow it.
 SwPlan sw_plan(int b, int n, int h, int w) {
@@ -285,14 +252,14 @@ SwPlan sw_plan(int b, int n, int h, int w) {
   p.kp_cap = (p.rmax * p.ws + 15) & ~15;
   const int ew = (6 * p.ws + 18 + 7) & ~7;                 // staged elements of a row, whole runs of eight
   p.pd = ew / 2 + 4;                                       // + the second copy's shift, kept a multiple of 16 bytes
-  p.lds = p.kp_cap * kSwRowB + (2 * p.rmax + 5) * 2 * p.pd * 4;
+  p.lds = p.kp_cap * kTileRowB + (2 * p.rmax + 5) * 2 * p.pd * 4;
   if (p.lds > kSwLdsCap) return p;
   p.tiles = n / kSwTile;
   const long long rows = (long long)b * p.ho;
-  const long long want = std::max<long long>(1, std::min<long long>(rows, (kSwTarget + p.tiles - 1) / p.tiles));
   // ... but a split is at least one full step: its five halo rows of x are loaded once per step
-  p.rows_per_split = (int)std::max<long long>((rows + want - 1) / want, std::min<long long>(rows, p.rmax));
-  p.splits = (int)((rows + p.rows_per_split - 1) / p.rows_per_split);
+  const RowSplit sp = split_rows(rows, p.tiles, kSwTarget, 1, std::min<long long>(rows, p.rmax));
+  p.rows_per_split = sp.per;
+  p.splits = sp.count;
   p.ok = 1;
   return p;
 }
@@ -331,15 +298,7 @@ int launch_stem_conv_wgrad(const void* dy, const void* x, float* part, void* dw,
   a.inv_ws = 1.0f / (float)p.ws; a.inv_runs = 1.0f / (float)(p.pd / 4 - 1);
   const int rc = dtype == MRLA_F16 ? sw_launch<f16_t>(p, a, dy, x, part, st) : sw_launch<bf16_t>(p, a, dy, x, part, st);
   if (rc != MRLA_OK) return rc;
-  const int total4 = n * 147 / 4;
-  const dim3 grid((total4 + 255) / 256), block(256);
-  if (dw_f32)      // the fp32 master weight's gradient directly
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel<float>, grid, block, 0, st, part, (float*)dw, p.splits, total4);
-  else if (dtype == MRLA_F16)
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel<f16_t>, grid, block, 0, st, part, (f16_t*)dw, p.splits, total4);
-  else
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel<bf16_t>, grid, block, 0, st, part, (bf16_t*)dw, p.splits, total4);
-  return hip_status(hipGetLastError());
+  return launch_split_sum(part, dw, dw_f32, dtype, p.splits, n * 147, st);
 }
 
 }  // namespace mrla

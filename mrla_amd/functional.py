@@ -77,15 +77,22 @@ CONV1X1_F32 = False   # an fp32 channels_last 1x1 convolution outside autocast (
 #                        on for a block of code.  profiles/conv1x1_f32.md has the numbers a change of the default rests on.
 
 
-@contextlib.contextmanager
-def fp32_gemms(enabled=True):
-    """CONV1X1_F32 = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
-    global CONV1X1_F32
-    prev, CONV1X1_F32 = CONV1X1_F32, bool(enabled)
-    try:
-        yield
-    finally:
-        CONV1X1_F32 = prev
+def _switch(flag, name):
+    """The context manager `name` of the module-level switch `flag`."""
+    @contextlib.contextmanager
+    def manager(enabled=True):
+        g = globals()
+        prev, g[flag] = g[flag], bool(enabled)
+        try:
+            yield
+        finally:
+            g[flag] = prev
+    manager.__name__ = manager.__qualname__ = name
+    manager.__doc__ = f"{flag} = `enabled` inside the block; the previous value comes back on exit, also when the block raises."
+    return manager
+
+
+fp32_gemms = _switch("CONV1X1_F32", "fp32_gemms")
 
 
 CONV3X3_WGRAD = False   # the weight gradient of an eligible 3x3 convolution (conv3x3_applies: the bottleneck's conv2, both of the
@@ -97,15 +104,7 @@ CONV3X3_WGRAD = False   # the weight gradient of an eligible 3x3 convolution (co
 #                         profiles/conv3x3_wgrad.md has the numbers a change of the default rests on.
 
 
-@contextlib.contextmanager
-def conv3x3_wgrad(enabled=True):
-    """CONV3X3_WGRAD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
-    global CONV3X3_WGRAD
-    prev, CONV3X3_WGRAD = CONV3X3_WGRAD, bool(enabled)
-    try:
-        yield
-    finally:
-        CONV3X3_WGRAD = prev
+conv3x3_wgrad = _switch("CONV3X3_WGRAD", "conv3x3_wgrad")
 
 
 CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_applies: the bottleneck's conv2, both of the basic
@@ -119,15 +118,7 @@ CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_
 #                       the default rests on.
 
 
-@contextlib.contextmanager
-def conv3x3_fwd(enabled=True):
-    """CONV3X3_FWD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
-    global CONV3X3_FWD
-    prev, CONV3X3_FWD = CONV3X3_FWD, bool(enabled)
-    try:
-        yield
-    finally:
-        CONV3X3_FWD = prev
+conv3x3_fwd = _switch("CONV3X3_FWD", "conv3x3_fwd")
 
 
 STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolution of three channels (stem_conv_applies: conv1 of
@@ -138,15 +129,7 @@ STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolut
 #                      numbers a change of the default rests on.
 
 
-@contextlib.contextmanager
-def stem_wgrad(enabled=True):
-    """STEM_WGRAD = `enabled` inside the block; the previous value comes back on exit, also when the block raises."""
-    global STEM_WGRAD
-    prev, STEM_WGRAD = STEM_WGRAD, bool(enabled)
-    try:
-        yield
-    finally:
-        STEM_WGRAD = prev
+stem_wgrad = _switch("STEM_WGRAD", "stem_wgrad")
 
 
 @contextlib.contextmanager
@@ -2071,11 +2054,68 @@ def conv1x1_applies(conv, x, strided=False):
     return torch.is_grad_enabled() and conv.weight.requires_grad and lib.mrla_conv1x1_wgrad_rows(m, k, n, dt) > 0
 
 
-def _conv3x3_dtype(x):
+def _conv_compute_dtype(x):
     """The dtype the stock convolution of `x` computes in: autocast's under CUDA autocast, else x's own."""
     if x.is_cuda and torch.is_autocast_enabled("cuda"):
         return torch.get_autocast_dtype("cuda")
     return x.dtype
+
+
+def _spatial_conv_applies(conv, x, kernel, strides, padding, want_wgrad):
+    """The compute dtype where `conv(x)` is a convolution the own spatial kernels take, else None: a bias-free nn.Conv2d of
+    this kernel size and padding, one of `strides`, dilation 1, groups 1, zero padding; a CUDA channels_last 16-byte-aligned
+    input of conv's channels that the convolution computes in bf16 or fp16 (its own dtype, or autocast's) on a CUDA weight
+    of that dtype (as stored, or as autocast casts it); with `want_wgrad`, grad mode and a weight that wants its gradient."""
+    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == kernel and conv.stride in strides and conv.padding == padding
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"):
+        return None
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
+        return None
+    wt = conv.weight
+    if want_wgrad and not (torch.is_grad_enabled() and wt.requires_grad):
+        return None
+    if not (wt.is_cuda and x.shape[1] == conv.in_channels):
+        return None
+    dt, auto = _conv_compute_dtype(x), torch.is_autocast_enabled("cuda")
+    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
+        return None
+    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+        return None
+    return dt
+
+
+def _own_wgrad(ctx, entry, rows_entry, dy, x, shape, taps):
+    """The weight gradient [n, *taps] of a spatial convolution from its own entry point, in the weight's own dtype and laid
+    out as a channels_last [n, c, kh, kw]; None where the kernel does not take the shape (`shape`: the entry point's
+    integers in front of the dtype)."""
+    dt = _DT[x.dtype]
+    rows = getattr(L.load(), rows_entry)(*shape, dt)
+    if rows <= 0:
+        return None
+    n, (kh, kw, c) = dy.shape[1], taps
+    part = torch.empty((rows, n, kh * kw * c), dtype=torch.float32, device=x.device)
+    gw = torch.empty((n, c, kh, kw), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
+    _call(entry, (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), *shape, dt,
+          _DT[ctx.wdtype], _stream())
+    return gw
+
+
+def _stock_conv_backward(ctx, dy, x, w16, stride, padding, gx, gw):
+    """(gx, gw) with whatever is asked for and still None taken from the stock backward, masked to exactly that."""
+    need_x, need_w = ctx.needs_input_grad[0] and gx is None, ctx.needs_input_grad[1] and gw is None
+    if need_x or need_w:
+        gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
+                                                          [need_x, need_w, False])
+        gx = gx2 if need_x else gx
+        gw = gw2.to(ctx.wdtype) if need_w else gw
+    return gx, gw
+
+
+def _weight_strides(ctx, gw):
+    """`gw` in the weight's own strides (autograd's / DDP's layout contract)."""
+    if gw is not None and gw.stride() != ctx.wstride:
+        gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
+    return gw
 
 
 def conv3x3_applies(conv, x):
@@ -2083,19 +2123,8 @@ def conv3x3_applies(conv, x):
     dilation 1 / groups 1 / stride (1, 1) or (2, 2) whose weight wants its gradient, a CUDA channels_last input that the
     convolution computes in bf16 or fp16 (its own dtype, or autocast's), and a shape the kernel takes (mrla_conv3x3_wgrad_rows).
     Frozen stages, ResNeXt groups, dilated detection variants, NCHW and fp32 keep the stock path."""
-    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride in ((1, 1), (2, 2))
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.padding_mode == "zeros"):
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
-        return False
-    wt = conv.weight
-    if not (torch.is_grad_enabled() and wt.requires_grad and wt.is_cuda and x.shape[1] == conv.in_channels):
-        return False
-    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
-    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
-        return False
-    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+    dt = _spatial_conv_applies(conv, x, (3, 3), ((1, 1), (2, 2)), (1, 1), True)
+    if dt is None:
         return False
     b, c, h, w = x.shape
     return L.load().mrla_conv3x3_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
@@ -2120,28 +2149,14 @@ class _Conv3x3Fn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy):
         x, w16 = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dy = dy.contiguous(memory_format=_CL)
         b, c, h, wd = x.shape
-        n = w16.shape[0]
-        gx = gw = None
-        if need_w and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
-            dt = _DT[x.dtype]
-            rows = L.load().mrla_conv3x3_wgrad_rows(b, c, n, h, wd, ctx.stride[0], dt)
-            if rows > 0:
-                part = torch.empty((rows, n, 9, c), dtype=torch.float32, device=x.device)
-                gw = torch.empty((n, c, 3, 3), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
-                _call("mrla_conv3x3_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
-                      b, c, n, h, wd, ctx.stride[0], dt, _DT[ctx.wdtype], _stream())
-                need_w = False
-        if need_x or need_w:
-            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1,
-                                                              [need_x, need_w, False])
-            gx = gx2 if need_x else None
-            gw = gw2.to(ctx.wdtype) if need_w else gw
-        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
-            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
-        return gx, gw, None
+        gw = None
+        if ctx.needs_input_grad[1] and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
+            gw = _own_wgrad(ctx, "mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows", dy, x,
+                            (b, c, w16.shape[0], h, wd, ctx.stride[0]), (3, 3, c))
+        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), None, gw)
+        return gx, _weight_strides(ctx, gw), None
 
 
 def conv3x3_fwd_applies(conv, x):
@@ -2149,19 +2164,8 @@ def conv3x3_fwd_applies(conv, x):
     conv3x3_applies (a bias-free nn.Conv2d 3x3 / padding 1 / dilation 1 / groups 1 / stride (1, 1) or (2, 2), a CUDA
     channels_last 16-byte-aligned input computed in bf16 or fp16, a shape the kernel takes: mrla_conv3x3_fwd_rows) -- but
     neither grad mode nor a weight that wants its gradient: inference and frozen stages qualify."""
-    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride in ((1, 1), (2, 2))
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.padding_mode == "zeros"):
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
-        return False
-    wt = conv.weight
-    if not (wt.is_cuda and x.shape[1] == conv.in_channels):
-        return False
-    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
-    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
-        return False
-    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+    dt = _spatial_conv_applies(conv, x, (3, 3), ((1, 1), (2, 2)), (1, 1), False)
+    if dt is None:
         return False
     b, c, h, w = x.shape
     return L.load().mrla_conv3x3_fwd_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
@@ -2211,31 +2215,18 @@ class _Conv3x3FwdFn(torch.autograd.Function):
         own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
         gx = gw = None
         if need_w and own and ctx.own_wgrad:
-            rows = L.load().mrla_conv3x3_wgrad_rows(b, c, n, h, wd, ctx.stride[0], dt)
-            if rows > 0:
-                part = torch.empty((rows, n, 9, c), dtype=torch.float32, device=x.device)
-                gw = torch.empty((n, c, 3, 3), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
-                _call("mrla_conv3x3_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
-                      b, c, n, h, wd, ctx.stride[0], dt, _DT[ctx.wdtype], _stream())
-                need_w = False
+            gw = _own_wgrad(ctx, "mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows", dy, x, (b, c, n, h, wd, ctx.stride[0]), (3, 3, c))
         if need_x and own and ctx.stride[0] == 1:
             wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
             gx = torch.empty_like(x)
             _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
                   b, n, c, h, wd, 1, dt, _stream())
-            need_x = False
-        if need_x or need_w:
-            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1,
-                                                              [need_x, need_w, False])
-            gx = gx2 if need_x else gx
-            gw = gw2.to(ctx.wdtype) if need_w else gw
-        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
-            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
-        return gx, gw, None, None, None
+        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), gx, gw)
+        return gx, _weight_strides(ctx, gw), None, None, None
 
 
 def _conv3x3_own(x, conv, moments):
-    dt = _conv3x3_dtype(x)
+    dt = _conv_compute_dtype(x)
     return _Conv3x3FwdFn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], moments,
                                CONV3X3_WGRAD and conv3x3_applies(conv, x))
 
@@ -2250,7 +2241,7 @@ def conv3x3(x, conv):
         return _conv3x3_own(x, conv, False)[0]
     if not (CONV3X3_WGRAD and conv3x3_applies(conv, x)):
         return conv(x)
-    dt = _conv3x3_dtype(x)
+    dt = _conv_compute_dtype(x)
     return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0])
 
 
@@ -2270,19 +2261,8 @@ def stem_conv_applies(conv, x):
     padding (3, 3) / dilation 1 / groups 1 of three input channels whose weight wants its gradient, a CUDA channels_last
     16-byte-aligned input that the convolution computes in bf16 or fp16 (its own dtype, or autocast's), and a shape the kernel
     takes (mrla_stem_conv_wgrad_rows).  Everything else keeps the stock path."""
-    if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
-            and conv.in_channels == 3):
-        return False
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.is_contiguous(memory_format=_CL) and x.data_ptr() % 16 == 0):
-        return False
-    wt = conv.weight
-    if not (torch.is_grad_enabled() and wt.requires_grad and wt.is_cuda and x.shape[1] == 3):
-        return False
-    dt, auto = _conv3x3_dtype(x), torch.is_autocast_enabled("cuda")
-    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
-        return False
-    if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
+    dt = _spatial_conv_applies(conv, x, (7, 7), ((2, 2),), (3, 3), True)
+    if dt is None or conv.in_channels != 3:
         return False
     b, _, h, w = x.shape
     return L.load().mrla_stem_conv_wgrad_rows(b, conv.out_channels, h, w, _DT[dt]) > 0
@@ -2307,28 +2287,13 @@ class _StemConvFn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy):
         x, w16 = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dy = dy.contiguous(memory_format=_CL)
         b, _, h, wd = x.shape
-        n = w16.shape[0]
-        gx = gw = None
-        if need_w and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
-            dt = _DT[x.dtype]
-            rows = L.load().mrla_stem_conv_wgrad_rows(b, n, h, wd, dt)
-            if rows > 0:
-                part = torch.empty((rows, n, 147), dtype=torch.float32, device=x.device)
-                gw = torch.empty((n, 3, 7, 7), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
-                _call("mrla_stem_conv_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw),
-                      b, n, h, wd, dt, _DT[ctx.wdtype], _stream())
-                need_w = False
-        if need_x or need_w:
-            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1,
-                                                              [need_x, need_w, False])
-            gx = gx2 if need_x else None
-            gw = gw2.to(ctx.wdtype) if need_w else gw
-        if gw is not None and gw.stride() != ctx.wstride:       # the weight's own strides (autograd's / DDP's layout contract)
-            gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
-        return gx, gw
+        gw = None
+        if ctx.needs_input_grad[1] and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
+            gw = _own_wgrad(ctx, "mrla_stem_conv_wgrad", "mrla_stem_conv_wgrad_rows", dy, x, (b, w16.shape[0], h, wd), (7, 7, 3))
+        gx, gw = _stock_conv_backward(ctx, dy, x, w16, (2, 2), (3, 3), None, gw)
+        return gx, _weight_strides(ctx, gw)
 
 
 def stem_conv(x, conv):
@@ -2337,7 +2302,7 @@ def stem_conv(x, conv):
     the stock operator's and whose weight gradient is mrla_stem_conv_wgrad's."""
     if not (STEM_WGRAD and stem_conv_applies(conv, x)):
         return conv(x)
-    dt = _conv3x3_dtype(x)
+    dt = _conv_compute_dtype(x)
     return _StemConvFn.apply(x if x.dtype == dt else x.to(dt), conv.weight)
 
 

@@ -98,8 +98,8 @@ def table(own_dir, stock_dir):
     print("|---|---|---|---|---|---|---|")
     for (name, *_), o, s in zip(SHAPES, own, stock):
         assert len(o) == 2 * N, (name, len(o))
-        main = sum(ns for k, ns in o if "reduce" not in k) / N / 1e3
-        red = sum(ns for k, ns in o if "reduce" in k) / N / 1e3
+        main = sum(ns for k, ns in o if "split_sum" not in k) / N / 1e3
+        red = sum(ns for k, ns in o if "split_sum" in k) / N / 1e3
         st = sum(ns for _, ns in s) / N / 1e3
         kinds = {}
         for k, ns in s:

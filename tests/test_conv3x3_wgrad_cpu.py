@@ -111,7 +111,7 @@ def test_the_splits_tile_the_output_rows_exactly_once():
 def test_no_instance_of_the_new_file_uses_scratch():
     kernels = kr.kernel_resources("conv3x3_wgrad.hip")
     main = [k for k in kernels if "conv3x3_wgrad_kernel" in k["mangled"]]
-    assert len(main) == 4 and any("conv3x3_wgrad_reduce_kernel" in k["mangled"] for k in kernels)      # bf16 / fp16 x stride 1 / 2
+    assert len(main) == 4 and any("split_sum_kernel" in k["mangled"] for k in kernels)      # bf16 / fp16 x stride 1 / 2
     bad = {k["mangled"]: k["scratch"] for k in kernels if k["scratch"] != 0}
     assert not bad, f"instances with scratch (bytes per lane): {bad}"
     for k in main:           # __launch_bounds__(256, 2): the planner's two workgroups per CU

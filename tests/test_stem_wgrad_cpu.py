@@ -123,7 +123,7 @@ def test_the_splits_tile_the_output_rows_exactly_once_and_the_lds_stays_under_th
 def test_no_instance_of_the_new_file_uses_scratch():
     kernels = kr.kernel_resources("stem_wgrad.hip")
     main = [k for k in kernels if "stem_wgrad_kernel" in k["mangled"]]
-    assert len(main) == 2 and sum("stem_wgrad_reduce_kernel" in k["mangled"] for k in kernels) == 3      # bf16 / fp16; three dw types
+    assert len(main) == 2 and sum("split_sum_kernel" in k["mangled"] for k in kernels) == 3      # bf16 / fp16; three dw types
     bad = {k["mangled"]: k["scratch"] for k in kernels if k["scratch"] != 0}
     assert not bad, f"instances with scratch (bytes per lane): {bad}"
     for k in main:           # __launch_bounds__(256, 2): the planner's two workgroups per CU
