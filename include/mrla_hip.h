@@ -679,6 +679,31 @@ int mrla_conv3x3_fwd_plan(int b, int c, int n, int h, int w, int stride, int dty
 int mrla_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom_part /*[opt]*/, int b, int c, int n, int h, int w,
                      int stride, int dtype, void* stream);
 
+/* Input gradient of that 3x3 convolution at stride 2 in both directions, padding 1, dilation 1, groups 1, on the MFMA without
+ * zero taps (two ADDITIVE symbols, MRLA_ABI_VERSION stays 5) -- the backward of the reference's strided conv3x3 call sites,
+ * which the reference leaves to cuDNN: conv2 of the first bottleneck of stages 2-4 and the first convolution of the same
+ * basic blocks in resnet/models/resnet_mrla_light.py, and the same blocks of the mmdet backbone:
+ *     dx[b, yi, xi, c] = round( sum_{kh, kw, n} dy[b, yo, xo, n] * wt[n, kh, kw, c] )
+ *                        over the (kh, yo) with yi = 2*yo + kh - 1 and 0 <= yo < ho; likewise (kw, xo)
+ *   dy: [b, ho, wo, n] and dx: [b, h, w, c] channels_last activations of `dtype` (MRLA_BF16 or MRLA_F16), ho = (h-1)/2 + 1,
+ *   wo = (w-1)/2 + 1; a dy row or column at ho / wo contributes nothing (the row below an image's last dy row is not the next
+ *   image's first);
+ *   wt: [n, 3, 3, c] of `dtype` -- the FORWARD's weight as mrla_conv3x3_fwd takes it, no flipped or transposed copy; fp32
+ *   accumulation over all of n (in 64-chunks, ascending) and the 1, 2, 2 or 4 taps that the parity of (yi, xi) meets, in one
+ *   fixed order (no split of the reduction), ONE rounding to nearest even at the store.
+ * No atomics and no memset: every element of dx is written exactly once per call, nothing is read outside dy and wt, and
+ * the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from a replayed graph.
+ * MRLA_EUNSUPPORTED unless c % 64 == 0, n % 64 == 0, dtype MRLA_BF16 or MRLA_F16 and b * h * w * max(c, n) * 2 < 2^31; any
+ * b, h, w >= 1 within that (odd sizes, 1x1 maps, rows wider than a step).  MRLA_EINVAL, decided on the host before anything
+ * is launched: a non-positive dimension, a dtype code that is none, a NULL pointer (`out` included), a pointer that is not
+ * 16-byte aligned.  The query answers the same code as the launch for the same arguments. */
+/* Host-side query, `out` is a HOST array of 6 ints: tile c, cell rows per workgroup range (cell row i of an image = its dx
+ * rows 2i and 2i + 1 = its dy row i; numbered image after image, b * ho in all), cell rows per step, column segments per row,
+ * ranges, workgroups.  Range i takes the cell rows [i * out[1], min(b * ho, (i + 1) * out[1])); a workgroup is one
+ * (range, 64-channel tile of c). */
+int mrla_conv3x3_dgrad_s2_plan(int b, int c, int n, int h, int w, int dtype, int* out);
+int mrla_conv3x3_dgrad_s2(const void* dy, const void* wt, void* dx, int b, int c, int n, int h, int w, int dtype, void* stream);
+
 /* Weight gradient of the stem convolution: 7x7, stride 2, padding 3, dilation 1, groups 1, three input channels (three
  * ADDITIVE symbols, MRLA_ABI_VERSION stays 5) -- the backward of conv1 of resnet/models/resnet_mrla_light.py, which the
  * reference leaves to cuDNN:

@@ -19,7 +19,10 @@ def __getattr__(name):
     if name == "conv3x3_fwd":      # the switch of the own 3x3 forward and stride-1 input gradient (functional.CONV3X3_FWD)
         from . import functional
         return functional.conv3x3_fwd
-    if name == "stem_wgrad":       # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
+    if name == "conv3x3_dgrad":    # the switch of the own stride-2 3x3 input gradient (functional.CONV3X3_DGRAD)
+        from . import functional
+        return functional.conv3x3_dgrad
+    if name == "stem_wgrad":      # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
         from . import functional
         return functional.stem_wgrad
     if name == "reproducible_gradients":      # both of them: every parameter gradient a function of the step's inputs alone

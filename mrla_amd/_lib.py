@@ -119,6 +119,8 @@ SIGNATURES = {
     "mrla_conv3x3_fwd_rows": [_I] * 7,
     "mrla_conv3x3_fwd_plan": [_I] * 7 + [_P],
     "mrla_conv3x3_fwd": [_P, _P, _P, _P] + [_I] * 7 + [_P],
+    "mrla_conv3x3_dgrad_s2_plan": [_I] * 6 + [_P],
+    "mrla_conv3x3_dgrad_s2": [_P, _P, _P] + [_I] * 6 + [_P],
     "mrla_stem_conv_wgrad_rows": [_I] * 5,
     "mrla_stem_conv_wgrad_plan": [_I] * 5 + [_P],
     "mrla_stem_conv_wgrad": [_P, _P, _P, _P] + [_I] * 6 + [_P],
@@ -215,6 +217,12 @@ def conv3x3_fwd_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, output rows per workgroup, rows per step, segments per row, record rows, workgroups) of mrla_conv3x3_fwd, or
     None."""
     return _spatial_plan("mrla_conv3x3_fwd_plan", 6, (b, c, n, h, w, stride), dtype)
+
+
+def conv3x3_dgrad_s2_plan(b, c, n, h, w, dtype=None):
+    """(tile c, cell rows per workgroup range, cell rows per step, segments per row, ranges, workgroups) of
+    mrla_conv3x3_dgrad_s2, or None."""
+    return _spatial_plan("mrla_conv3x3_dgrad_s2_plan", 6, (b, c, n, h, w), dtype)
 
 
 def stem_conv_wgrad_plan(b, n, h, w, dtype=None):

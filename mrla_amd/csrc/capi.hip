@@ -756,7 +756,7 @@ int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int
   return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
-// The spatial convolutions (conv3x3_wgrad.hip, conv3x3_fwd.hip, stem_wgrad.hip).  One argument check for the queries and the
+// The spatial convolutions (conv3x3_wgrad.hip, conv3x3_fwd.hip, conv3x3_dgrad.hip, stem_wgrad.hip).  One argument check for the queries and the
 // launches of a shape, so that they answer the same code for the same arguments.
 static int conv3x3_args(int b, int c, int n, int h, int w, int stride, int dtype) {
   if (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || stride <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
@@ -815,6 +815,21 @@ int mrla_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom_part, in
   const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
   if (rc != MRLA_OK) return rc;
   return launch_conv3x3_fwd(x, wt, y, mom_part, b, c, n, h, w, stride, dtype, (hipStream_t)stream);
+}
+
+int mrla_conv3x3_dgrad_s2_plan(int b, int c, int n, int h, int w, int dtype, int* out) {
+  if (!out) return MRLA_EINVAL;
+  const int rc = conv3x3_args(b, c, n, h, w, 2, dtype);
+  return rc != MRLA_OK ? rc : conv3x3_dgrad_s2_plan(b, c, n, h, w, out);
+}
+
+int mrla_conv3x3_dgrad_s2(const void* dy, const void* wt, void* dx, int b, int c, int n, int h, int w, int dtype, void* stream) {
+  if (!dy || !wt || !dx) return MRLA_EINVAL;
+  // a lane moves 16 bytes of dy and wt and 8 of dx
+  if (((uintptr_t)dy | (uintptr_t)wt | (uintptr_t)dx) & 15) return MRLA_EINVAL;
+  const int rc = conv3x3_args(b, c, n, h, w, 2, dtype);
+  if (rc != MRLA_OK) return rc;
+  return launch_conv3x3_dgrad_s2(dy, wt, dx, b, c, n, h, w, dtype, (hipStream_t)stream);
 }
 
 int mrla_stem_conv_wgrad_rows(int b, int n, int h, int w, int dtype) {

@@ -1,4 +1,4 @@
-// What the spatial-convolution kernels (conv3x3_wgrad.hip, stem_wgrad.hip, conv3x3_fwd.hip) share, written once: the
+// What the spatial-convolution kernels (conv3x3_wgrad.hip, stem_wgrad.hip, conv3x3_fwd.hip, conv3x3_dgrad.hip) share, written once: the
 // transposing LDS read and its lane geometry, the swizzled offset of a 128-byte tile row, the walk of a workgroup over its
 // output rows, the fixed-order sum of fp32 partial tiles, and on the host the 3x3 raster geometry and the split of the
 // output rows over workgroups.  Everything has internal linkage: each of the three translation units compiles its own

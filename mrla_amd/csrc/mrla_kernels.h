@@ -238,6 +238,11 @@ int conv3x3_fwd_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_fwd_plan(int b, int c, int n, int h, int w, int s, int* out);
 int launch_conv3x3_fwd(const void* x, const void* wt, void* y, float* mom, int b, int c, int n, int h, int w, int s, int dtype,
                        hipStream_t st);
+// conv3x3_dgrad.hip -- the input gradient of that convolution at stride 2 (bf16 or fp16), dx [b,h,w,c] from dy [b,ho,wo,n] and
+// the forward's own wt [n,3,3,c]: four parity classes per 2x2 cell of dx, nine taps, no zero-inserted dy
+int conv3x3_dgrad_s2_plan(int b, int c, int n, int h, int w, int* out);
+int launch_conv3x3_dgrad_s2(const void* dy, const void* wt, void* dx, int b, int c, int n, int h, int w, int dtype,
+                            hipStream_t st);
 // stem_wgrad.hip -- the weight gradient of the stem's 7x7 / stride 2 / padding 3 convolution of three channels, dW [n,7,7,3],
 // as one product of dY^T and the pixels' seven 21-element windows (bf16 or fp16); part [rows][n][7][7][3]
 int stem_conv_wgrad_rows(int b, int n, int h, int w);

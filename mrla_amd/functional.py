@@ -113,12 +113,25 @@ CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_
 #                       from run to run -- and so does its input gradient at stride 1 (the same kernel on the flipped,
 #                       transposed weight); in front of a train-mode BatchNorm the kernel hands over the moment records and
 #                       the separate moments pass over its output is gone (conv3x3_bn_act).  The stride-2 input gradient
-#                       stays the stock operator's.  False (the default): the very same autograd graph and launches as before;
-#                       conv3x3_fwd() turns it on for a block of code.  profiles/conv3x3_fwd.md has the numbers a change of
-#                       the default rests on.
+#                       is the stock operator's unless CONV3X3_DGRAD is on as well.  False (the default): the very same
+#                       autograd graph and launches as before; conv3x3_fwd() turns it on for a block of code.
+#                       profiles/conv3x3_fwd.md has the numbers a change of the default rests on.
 
 
 conv3x3_fwd = _switch("CONV3X3_FWD", "conv3x3_fwd")
+
+
+CONV3X3_DGRAD = False   # the input gradient of an eligible stride-2 3x3 convolution (conv3x3_dgrad_applies: conv2 of the first
+#                         bottleneck of stages 2-4, the first convolution of the same basic blocks) comes from
+#                         mrla_conv3x3_dgrad_s2 -- four parity classes per 2x2 cell of dx, nine taps, all of n in one fixed
+#                         order on the forward's own weight: a function of its inputs alone, where the stock operator's
+#                         solver choice is not.  On its own: the stock forward and the stock weight gradient around it; with
+#                         CONV3X3_FWD and CONV3X3_WGRAD no product of a 3x3 call site is left to the stock library.  False
+#                         (the default): the very same autograd graph and launches as before; conv3x3_dgrad() turns it on
+#                         for a block of code.  profiles/conv3x3_dgrad.md has the numbers a change of the default rests on.
+
+
+conv3x3_dgrad = _switch("CONV3X3_DGRAD", "conv3x3_dgrad")
 
 
 STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolution of three channels (stem_conv_applies: conv1 of
@@ -2130,18 +2143,34 @@ def conv3x3_applies(conv, x):
     return L.load().mrla_conv3x3_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
 
 
+def _own_dgrad_s2(dy, x, w16):
+    """dX of a stride-2 3x3 convolution from mrla_conv3x3_dgrad_s2 on dy and the forward's own weight `w16` (channels_last
+    [n, c, 3, 3] = [n, 3, 3, c] in memory, 16-byte aligned)."""
+    b, c, h, wd = x.shape
+    gx = torch.empty_like(x)
+    _call("mrla_conv3x3_dgrad_s2", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(w16), _ptr(gx),
+          b, c, w16.shape[0], h, wd, _DT[x.dtype], _stream())
+    return gx
+
+
 class _Conv3x3Fn(torch.autograd.Function):
     """y = conv2d(x, w, stride, padding 1) of a channels_last bf16 or fp16 `x` by the stock operator, on `w` cast to x's dtype as
-    autocast casts it.  Backward: dX from the stock operator's backward with the weight gradient masked out (its split-K
-    weight-gradient solver is never invoked), dW [n, 3, 3, c] from mrla_conv3x3_wgrad in the weight's own dtype -- for an fp32
-    master weight the fp32 sums themselves, no 16-bit rounding and no cast kernel -- returned as [n, c, 3, 3]."""
+    autocast casts it.  Backward: dW [n, 3, 3, c] from mrla_conv3x3_wgrad where `own_wgrad` (CONV3X3_WGRAD and conv3x3_applies
+    at the call), in the weight's own dtype -- for an fp32 master weight the fp32 sums themselves, no 16-bit rounding and no
+    cast kernel -- returned as [n, c, 3, 3]; dX from mrla_conv3x3_dgrad_s2 where `own_dgrad` (CONV3X3_DGRAD and
+    conv3x3_dgrad_applies at the call); what is left from the stock operator's backward, masked to exactly that (its split-K
+    weight-gradient solver is never invoked under `own_wgrad`)."""
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, stride):
-        ctx.stride = (stride, stride)
+    def forward(ctx, x, w, stride, own_wgrad, own_dgrad):
+        ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
         ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
         w16 = w if w.dtype == x.dtype else w.to(x.dtype)
+        if own_dgrad:                                              # (the kernel reads the weight as [n, 3, 3, c], 16 bytes a lane)
+            w16 = w16.contiguous(memory_format=_CL)
+            if w16.data_ptr() % 16:
+                w16 = w16.clone(memory_format=_CL)
         ctx.save_for_backward(x, w16)
         return torch.ops.aten.convolution(x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1)
 
@@ -2151,12 +2180,15 @@ class _Conv3x3Fn(torch.autograd.Function):
         x, w16 = ctx.saved_tensors
         dy = dy.contiguous(memory_format=_CL)
         b, c, h, wd = x.shape
-        gw = None
-        if ctx.needs_input_grad[1] and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
+        own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
+        gx = gw = None
+        if ctx.needs_input_grad[1] and own and ctx.own_wgrad:
             gw = _own_wgrad(ctx, "mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows", dy, x,
                             (b, c, w16.shape[0], h, wd, ctx.stride[0]), (3, 3, c))
-        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), None, gw)
-        return gx, _weight_strides(ctx, gw), None
+        if ctx.needs_input_grad[0] and own and ctx.own_dgrad:
+            gx = _own_dgrad_s2(dy, x, w16)
+        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), gx, gw)
+        return gx, _weight_strides(ctx, gw), None, None, None
 
 
 def conv3x3_fwd_applies(conv, x):
@@ -2171,18 +2203,31 @@ def conv3x3_fwd_applies(conv, x):
     return L.load().mrla_conv3x3_fwd_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
 
 
+def conv3x3_dgrad_applies(conv, x):
+    """True when the input gradient of `conv(x)` belongs on mrla_conv3x3_dgrad_s2: the module, layout and dtype conditions of
+    conv3x3_fwd_applies, stride (2, 2), grad mode and an input that wants its gradient, and a shape the kernel takes
+    (mrla_conv3x3_dgrad_s2_plan).  A frozen weight qualifies; stride 1 has its own route (CONV3X3_FWD)."""
+    dt = _spatial_conv_applies(conv, x, (3, 3), ((2, 2),), (1, 1), False)
+    if dt is None or not (torch.is_grad_enabled() and x.requires_grad):
+        return False
+    b, c, h, w = x.shape
+    return L.conv3x3_dgrad_s2_plan(b, c, conv.out_channels, h, w, _DT[dt]) is not None
+
+
 class _Conv3x3FwdFn(torch.autograd.Function):
     """(y, records) = mrla_conv3x3_fwd of a channels_last bf16 or fp16 `x` on `w` cast to x's dtype as autocast casts it and
     laid out [n, 3, 3, c]; records: the [rows, n, MRLA_GEMM_MOMENTS] moment records of y for the BatchNorm behind it where
     `moments`, else empty.  Backward: dX at stride 1 from the same entry point on dy and the flipped, transposed weight (a
-    pure permutation), at stride 2 from the stock operator's backward; dW from mrla_conv3x3_wgrad where `own_wgrad`
-    (CONV3X3_WGRAD and conv3x3_applies at the call), else from the stock backward -- each masked to what is asked for."""
+    pure permutation), at stride 2 from mrla_conv3x3_dgrad_s2 on dy and the saved weight itself where `own_dgrad`
+    (CONV3X3_DGRAD and conv3x3_dgrad_applies at the call), else from the stock operator's backward; dW from
+    mrla_conv3x3_wgrad where `own_wgrad` (CONV3X3_WGRAD and conv3x3_applies at the call), else from the stock backward --
+    each masked to what is asked for."""
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, stride, moments, own_wgrad):
+    def forward(ctx, x, w, stride, moments, own_wgrad, own_dgrad):
         ctx.set_materialize_grads(False)
-        ctx.stride, ctx.own_wgrad = (stride, stride), own_wgrad
+        ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
         ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
         w16 = (w if w.dtype == x.dtype else w.to(x.dtype)).contiguous(memory_format=_CL)
         if w16.data_ptr() % 16:
@@ -2206,7 +2251,7 @@ class _Conv3x3FwdFn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy, _dpart=None):
         if dy is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         x, w16 = ctx.saved_tensors
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         dy = dy.contiguous(memory_format=_CL)
@@ -2221,28 +2266,32 @@ class _Conv3x3FwdFn(torch.autograd.Function):
             gx = torch.empty_like(x)
             _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
                   b, n, c, h, wd, 1, dt, _stream())
+        if need_x and own and ctx.own_dgrad:
+            gx = _own_dgrad_s2(dy, x, w16)
         gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), gx, gw)
-        return gx, _weight_strides(ctx, gw), None, None, None
+        return gx, _weight_strides(ctx, gw), None, None, None, None
 
 
 def _conv3x3_own(x, conv, moments):
     dt = _conv_compute_dtype(x)
     return _Conv3x3FwdFn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], moments,
-                               CONV3X3_WGRAD and conv3x3_applies(conv, x))
+                               CONV3X3_WGRAD and conv3x3_applies(conv, x), CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x))
 
 
 def conv3x3(x, conv):
     """conv(x) for the 3x3 convolutions of the blocks (resnet_mrla_light.py: conv2 of the bottleneck, both of the basic
-    block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, with
-    CONV3X3_WGRAD off, or where conv3x3_applies says no, it IS conv(x): the same autograd graph as before.
-    Otherwise one autograd node whose forward and input gradient are the stock operator's and whose weight gradient is
-    mrla_conv3x3_wgrad's."""
+    block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, where
+    neither CONV3X3_WGRAD with conv3x3_applies nor CONV3X3_DGRAD with conv3x3_dgrad_applies holds, it IS conv(x): the same
+    autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn) whose forward is the stock operator's, whose weight
+    gradient is mrla_conv3x3_wgrad's under the first and whose input gradient is mrla_conv3x3_dgrad_s2's under the second."""
     if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
         return _conv3x3_own(x, conv, False)[0]
-    if not (CONV3X3_WGRAD and conv3x3_applies(conv, x)):
+    own_wgrad = CONV3X3_WGRAD and conv3x3_applies(conv, x)
+    own_dgrad = CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x)
+    if not (own_wgrad or own_dgrad):
         return conv(x)
     dt = _conv_compute_dtype(x)
-    return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0])
+    return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], own_wgrad, own_dgrad)
 
 
 def conv3x3_bn_act(x, conv, bn, relu, defer=False):
