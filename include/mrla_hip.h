@@ -648,6 +648,13 @@ int mrla_conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int stride, int d
  * image) per split, LDS stages, splits (= mrla_conv3x3_wgrad_rows()), output tiles.  Split i takes the rows
  * [i * out[2], min(b * ho, (i + 1) * out[2])). */
 int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int dtype, int* out);
+/* Host-side query (one more ADDITIVE symbol, MRLA_ABI_VERSION stays 5): 1 where mrla_conv3x3_wgrad -- its kernel and its
+ * reduction -- is expected to take less device time on MI355X than everything the stock operator launches for the same
+ * gradient (solver, zero-fill, casts), else 0; the negative codes of mrla_conv3x3_wgrad_rows for the arguments it refuses.
+ * A rule in the plan's quantities (stride, steps per workgroup, output pixels per split), not a list of shapes; its
+ * derivation from measurements is profiles/conv3x3_wgrad.md section 7.  A hint for a caller that routes by shape: the
+ * launch itself takes every supported shape. */
+int mrla_conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int stride, int dtype);
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w,
                        int stride, int dtype, int dw_dtype, void* stream);
 

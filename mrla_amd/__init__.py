@@ -16,7 +16,10 @@ def __getattr__(name):
     if name == "conv3x3_wgrad":    # the switch of the own 3x3 weight gradient (functional.CONV3X3_WGRAD), as a context manager
         from . import functional
         return functional.conv3x3_wgrad
-    if name == "conv3x3_fwd":      # the switch of the own 3x3 forward and stride-1 input gradient (functional.CONV3X3_FWD)
+    if name == "conv3x3_wgrad_auto":   # ... and of its route by shape, where the library prefers it (functional.CONV3X3_WGRAD_AUTO)
+        from . import functional
+        return functional.conv3x3_wgrad_auto
+    if name == "conv3x3_fwd":    # the switch of the own 3x3 forward and stride-1 input gradient (functional.CONV3X3_FWD)
         from . import functional
         return functional.conv3x3_fwd
     if name == "conv3x3_dgrad":    # the switch of the own stride-2 3x3 input gradient (functional.CONV3X3_DGRAD)

@@ -115,6 +115,7 @@ SIGNATURES = {
     "mrla_conv1x1_wgrad_bn_dx": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv3x3_wgrad_rows": [_I] * 7,
     "mrla_conv3x3_wgrad_plan": [_I] * 7 + [_P],
+    "mrla_conv3x3_wgrad_preferred": [_I] * 7,
     "mrla_conv3x3_wgrad": [_P, _P, _P, _P] + [_I] * 8 + [_P],
     "mrla_conv3x3_fwd_rows": [_I] * 7,
     "mrla_conv3x3_fwd_plan": [_I] * 7 + [_P],

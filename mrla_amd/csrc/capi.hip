@@ -789,6 +789,11 @@ int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int d
   return rc != MRLA_OK ? rc : conv3x3_wgrad_plan(b, c, n, h, w, stride, out);
 }
 
+int mrla_conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int stride, int dtype) {
+  const int rc = conv3x3_args(b, c, n, h, w, stride, dtype);
+  return rc != MRLA_OK ? rc : conv3x3_wgrad_preferred(b, c, n, h, w, stride);
+}
+
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w, int stride,
                        int dtype, int dw_dtype, void* stream) {
   const int rc = wgrad_launch_args(dy, x, part, dw, dtype, dw_dtype, conv3x3_args(b, c, n, h, w, stride, dtype));

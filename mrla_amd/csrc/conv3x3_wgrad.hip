@@ -17,8 +17,15 @@
 // predicated like the X raster's: nothing is read outside x or dy.  The pad pixels of dY multiply into nothing (9/7 of the
 // MFMA work at a 7x7 map).
 //
-// The loader is register-staged (16-byte pieces, four in flight per lane) and synchronous; two workgroups per CU
-// (__launch_bounds__(256, 2), <= 80 KB of LDS each) overlap one's loads with the other's MFMAs.  Both MFMA operands are COLUMNS
+// The loader is register-staged (16-byte pieces) and runs ONE STEP AHEAD of the products: the global loads of step i + 1 -- the
+// dY raster and, at stride 1, the whole X raster (12 pieces, 48 registers); at stride 2 the dY raster and the first 128 rows of
+// the X raster (7 pieces), the rest of it synchronously as before, four pieces in flight -- are issued before the k-loop of
+// step i and stay outstanding across it; behind the k-loop come the barrier, the LDS writes (the compiler's vmcnt wait stands
+// in front of them, none in front of the first MFMA: checked in the ISA), the barrier, the next k-loop.  One LDS stage, as
+// before: the overlap is in registers (252 / 240 VGPRs at stride 1 / 2, no scratch, two waves per SIMD).  Two workgroups per CU
+// (__launch_bounds__(256, 2), <= 80 KB of LDS each) still overlap one's LDS writes with the other's MFMAs.  The arithmetic --
+// steps, k-steps, the nine taps and their order -- is what it was with the synchronous loader: part and dw are bit-equal to it
+// (scripts/conv3x3_wgrad_against_build.py).  profiles/conv3x3_wgrad.md section 7 has what it bought.  Both MFMA operands are COLUMNS
 // of the pixel-major tiles, read with gfx950's transposing LDS read (4 pixels x 16 channels per 16 lanes, every lane its own
 // address -- which is what lets the X operand step by s pixels); 16-byte chunk ch of tile row r sits at chunk position
 // ch ^ (((r >> 1) & 1) << 2) (conv1x1_wgrad.hip's swizzle for 128-byte rows): conflict-free at stride 1, two-way on the X
@@ -37,7 +44,7 @@ typedef c1_f32x16 c3_f32x16;
 
 constexpr int kC3Tile = 64;             // output tile: 64 n x 64 c (x 9 taps)
 constexpr int kC3Waves = 4;             // 2 x 2 waves, a 32 x 32 block of each tap per wave
-constexpr int kC3Stages = 1;            // LDS stages: the second workgroup of the CU is the overlap
+constexpr int kC3Stages = 1;            // LDS stages: the next step's pieces wait in registers, not in a second stage
 constexpr int kC3Target = 2 * 256;      // workgroups: two per CU (the sibling's CU count)
 constexpr int kC3MaxKP1 = 128;          // dY raster rows of a step at stride 1: (128 + 128 + 2*60 + 3) * 128 B = 48 KB at most
 constexpr int kC3MaxKP2 = 96;           // ... at stride 2, where the X raster has four times the pixels: (96 + 4*96 + 2*48 + 3 + 7)
@@ -81,6 +88,12 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
   const int rows = a.b * a.ho;
   const int r_begin = split * a.rows_per_split, r_end = min(rows, r_begin + a.rows_per_split);
   const int PY = a.py, PX = S * a.py;
+  // The loader's registers: the dY raster is one pass of 32 * kYPieces tile rows, and kPreX passes of 128 rows of the X raster
+  // are fetched a step ahead -- all of it at stride 1 (kXAllPre), where a later pass does not exist
+  constexpr int kYPieces = S == 1 ? 4 : 3, kPreX = S == 1 ? 2 : 1;
+  constexpr bool kXAllPre = S == 1;
+  static_assert(kC3MaxKP1 <= 128 && kC3MaxKP2 <= 96, "the dY raster of a step is one pass of the loader");
+  static_assert(kC3MaxKP1 + 2 * kC3MaxPY + 3 <= 256, "the X raster of a stride-1 step is two passes of the loader");
 
   const int wn = wave >> 1, wc = wave & 1;
   // (tr_krel, tr_col, tr_chunk and tr_sub of conv_spatial.h written out: through the helpers this kernel's prologue comes out
@@ -98,64 +111,129 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
 
   const int prow = tid >> 3, pch = tid & 7;                // the loader: 32 tile rows per pass, 8 pieces a row
   const u32x4 zero4 = {0u, 0u, 0u, 0u};
+  // (32-bit byte offsets from the uniform bases: the planner refuses tensors of 2^31 bytes, and a lane's address is one register)
+  const unsigned char* const dYb = reinterpret_cast<const unsigned char*>(dY);
+  const unsigned char* const Xb = reinterpret_cast<const unsigned char*>(X);
 
-  for (int r = r_begin; r < r_end;) {
+  // The walk over (step, column segment), one ahead of the products: the geometry of a segment of the step at row r
+  struct Seg {
+    int r, seg, img, yo0, R, xo0, ws;
+  };
+  auto seg_at = [&](int r, int seg) {
     const RowStep st = row_step(r, r_end, a.ho, a.rmax);
-    const int img = st.img, yo0 = st.yo0, R = st.R;
-    for (int seg = 0; seg < a.nseg; ++seg) {
-      const int xo0 = seg * a.ws, ws = min(a.ws, a.wo - xo0);
-      const int KP = (R * PY + 15) & ~15;
-      const int XT = S * KP + S * (S - 1) * PY * (R - 1) + 2 * PX + 3;
-      const int ty_need = S * (R - 1) + 3, cx_need = S * (ws - 1) + 3;      // X raster rows / columns some tap of this step reads
-      const int yi0 = yo0 * S - 1, xi0 = xo0 * S - 1;
-      __syncthreads();                                      // the previous step's reads are done
-      // ---- dY raster: rows [0, KP) ----
-      for (int p0 = 0; p0 < KP; p0 += 128) {
-        u32x4 v[4];
+    Seg g;
+    g.r = r; g.seg = seg; g.img = st.img; g.yo0 = st.yo0; g.R = st.R;
+    g.xo0 = seg * a.ws; g.ws = min(a.ws, a.wo - g.xo0);
+    return g;
+  };
+  // The pieces of the dY raster (one pass: KP <= 128) and of pass `pass` of the X raster, every load predicated on its own
+  // pixel, zeros elsewhere.  The pixel coordinates are computed behind the test against the raster's end, where a group of 32
+  // tile rows that no lane needs costs a compare and a branch (at a 7x7 map five of the twelve groups exist), and from a row
+  // number that is opaque to the optimiser: as loop invariants the coordinates of the twelve pieces are hoisted out of the
+  // step loop and then spilled around the products -- recomputing them is four instructions a piece
+  auto load_y = [&](const Seg& g, u32x4 (&v)[kYPieces]) {
+    const int KP = (g.R * PY + 15) & ~15;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int p = p0 + 32 * u + prow;
-          const int ry = (int)(((float)p + 0.5f) * a.inv_py), j = p - ry * PY;
-          v[u] = zero4;
-          if (p < KP && ry < R && j < ws)
-            v[u] = *reinterpret_cast<const u32x4*>(dY + ((size_t)((img * a.ho + yo0 + ry) * a.wo + xo0 + j) * a.n + n0 + pch * 8));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int p = p0 + 32 * u + prow;
-          if (p < KP) *reinterpret_cast<u32x4*>(ty_tile + c3_off(p, pch)) = v[u];
-        }
+    for (int u = 0; u < kYPieces; ++u) {
+      int p = 32 * u + prow;
+      v[u] = zero4;
+      if (p < KP) {
+        asm volatile("" : "+v"(p));
+        const int ry = (int)(((float)p + 0.5f) * a.inv_py), j = p - ry * PY;
+        if (ry < g.R && j < g.ws)
+          v[u] = *reinterpret_cast<const u32x4*>(dYb + 2u * (unsigned)(((g.img * a.ho + g.yo0 + ry) * a.wo + g.xo0 + j) * a.n + n0 + pch * 8));
       }
-      // ---- X raster: rows [0, XT) ----
-      for (int t0 = 0; t0 < XT; t0 += 128) {
-        u32x4 v[4];
+    }
+  };
+  auto load_x = [&](const Seg& g, int pass, u32x4 (&v)[4]) {
+    const int KP = (g.R * PY + 15) & ~15;
+    const int XT = S * KP + S * (S - 1) * PY * (g.R - 1) + 2 * PX + 3;
+    const int ty_need = S * (g.R - 1) + 3, cx_need = S * (g.ws - 1) + 3;    // X raster rows / columns some tap of this step reads
+    const int yi0 = g.yo0 * S - 1, xi0 = g.xo0 * S - 1;
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = t0 + 32 * u + prow;
-          const int ty = (int)(((float)t + 0.5f) * a.inv_px), cx = t - ty * PX;
-          const int yi = yi0 + ty, xi = xi0 + cx;
-          v[u] = zero4;
-          if (t < XT && ty < ty_need && cx < cx_need && yi >= 0 && yi < a.h && xi >= 0 && xi < a.w)
-            v[u] = *reinterpret_cast<const u32x4*>(X + ((size_t)((img * a.h + yi) * a.w + xi) * a.c + c0 + pch * 8));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = t0 + 32 * u + prow;
-          if (t < XT) *reinterpret_cast<u32x4*>(tx_tile + c3_off(t, pch)) = v[u];
-        }
+    for (int u = 0; u < 4; ++u) {
+      int t = 128 * pass + 32 * u + prow;
+      v[u] = zero4;
+      if (t < XT) {
+        asm volatile("" : "+v"(t));
+        const int ty = (int)(((float)t + 0.5f) * a.inv_px), cx = t - ty * PX;
+        const int yi = yi0 + ty, xi = xi0 + cx;
+        if (ty < ty_need && cx < cx_need && yi >= 0 && yi < a.h && xi >= 0 && xi < a.w)
+          v[u] = *reinterpret_cast<const u32x4*>(Xb + 2u * (unsigned)(((g.img * a.h + yi) * a.w + xi) * a.c + c0 + pch * 8));
       }
-      __syncthreads();
-      // ---- nine products over the step's pixels ----
-      for (int k0 = 0; k0 < KP; k0 += 16) {
-        const int k = k0 + krel;
-        const typename Elem16<T>::x8 fa = c3_frag<T>(ty_tile, k, k + 4, chA, subA);
-        // the X raster row of dY raster row p = ry*PY + j under tap (0, 0): (S*ry)*PX + S*j = S*p + S*(S-1)*PY*ry (the tail
-        // behind the step's last row, all zeros in dY, stays inside the raster with ry held at R - 1)
-        int xr = S * k, xr2 = S * (k + 4);
-        if (S > 1) {
-          xr += S * (S - 1) * PY * min((int)(((float)k + 0.5f) * a.inv_py), R - 1);
-          xr2 += S * (S - 1) * PY * min((int)(((float)k + 4.5f) * a.inv_py), R - 1);
+    }
+  };
+  auto store_x = [&](int XT, int pass, const u32x4 (&v)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int t = 128 * pass + 32 * u + prow;
+      if (t < XT) *reinterpret_cast<u32x4*>(tx_tile + c3_off(t, pch)) = v[u];
+    }
+  };
+
+  u32x4 vy[kYPieces], vx[kPreX > 0 ? kPreX : 1][4];        // the prefetched pieces of the step to come
+  Seg cur = seg_at(r_begin, 0);
+  bool more = r_begin < r_end;                              // (the planner leaves no range empty)
+  if (more) {
+    load_y(cur, vy);
+#pragma unroll
+    for (int i = 0; i < kPreX; ++i) load_x(cur, i, vx[i]);
+  }
+  while (more) {
+    const int R = cur.R;
+    const int KP = (R * PY + 15) & ~15;
+    const int XT = S * KP + S * (S - 1) * PY * (R - 1) + 2 * PX + 3;
+    __syncthreads();                                        // the previous step's reads are done
+    // ---- dY raster: rows [0, KP); X raster: rows [0, XT), the prefetched passes, then the rest synchronously ----
+#pragma unroll
+    for (int u = 0; u < kYPieces; ++u) {
+      const int p = 32 * u + prow;
+      if (p < KP) *reinterpret_cast<u32x4*>(ty_tile + c3_off(p, pch)) = vy[u];
+    }
+#pragma unroll
+    for (int i = 0; i < kPreX; ++i) store_x(XT, i, vx[i]);
+    if (!kXAllPre)
+      for (int pass = kPreX; pass * 128 < XT; ++pass) {
+        u32x4 v[4];
+        load_x(cur, pass, v);
+        store_x(XT, pass, v);
+      }
+    __syncthreads();
+    // ---- the next step's loads go out under this step's products ----
+    Seg nxt = cur;
+    more = cur.seg + 1 < a.nseg || cur.r + R < r_end;
+    if (more) {
+      nxt = cur.seg + 1 < a.nseg ? seg_at(cur.r, cur.seg + 1) : seg_at(cur.r + R, 0);
+      load_y(nxt, vy);
+#pragma unroll
+      for (int i = 0; i < kPreX; ++i) load_x(nxt, i, vx[i]);
+    }
+    // ---- nine products over the step's pixels ----
+    for (int k0 = 0; k0 < KP; k0 += 16) {
+      const int k = k0 + krel;
+      const typename Elem16<T>::x8 fa = c3_frag<T>(ty_tile, k, k + 4, chA, subA);
+      // the X raster row of dY raster row p = ry*PY + j under tap (0, 0): (S*ry)*PX + S*j = S*p + S*(S-1)*PY*ry (the tail
+      // behind the step's last row, all zeros in dY, stays inside the raster with ry held at R - 1)
+      int xr = S * k, xr2 = S * (k + 4);
+      if (S > 1) {
+        xr += S * (S - 1) * PY * min((int)(((float)k + 0.5f) * a.inv_py), R - 1);
+        xr2 += S * (S - 1) * PY * min((int)(((float)k + 4.5f) * a.inv_py), R - 1);
+      }
+      if constexpr (S == 1) {
+        // the X operand of tap t + 1 is read while tap t multiplies: 5 - 7 % of the kernel at the ResNet-50 shapes (at stride
+        // 2, where those reads are two-way bank-conflicted, the same order measured 2 - 4 % SLOWER: the loop below stays)
+        typename Elem16<T>::x8 fb = c3_frag<T>(tx_tile, xr, xr2, chB, subB);
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+          typename Elem16<T>::x8 fbn = fb;
+          if (t < 8) {
+            const int off = ((t + 1) / 3) * PX + (t + 1) % 3;
+            fbn = c3_frag<T>(tx_tile, xr + off, xr2 + off, chB, subB);
+          }
+          Elem16<T>::mfma(acc[t], fa, fb);
+          fb = fbn;
         }
+      } else {
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
@@ -165,7 +243,7 @@ __device__ __forceinline__ void conv3x3_wgrad_body(const T* __restrict__ dY, con
           }
       }
     }
-    r += R;
+    cur = nxt;
   }
 
   // ---- partial tile: D[i][j], j = lane % 32 (c) on the lane, i = 8*(e/4) + 4*(lane/32) + e%4 (n) in register e ----
@@ -219,6 +297,22 @@ int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out) {
   if (!p.ok) return MRLA_EUNSUPPORTED;
   out[0] = kC3Tile; out[1] = kC3Tile; out[2] = p.rows_per_split; out[3] = kC3Stages; out[4] = p.splits; out[5] = p.tiles;
   return MRLA_OK;
+}
+
+// 1 where the kernel and its reduction are expected to take less device time than everything the stock operator launches for
+// this gradient.  profiles/conv3x3_wgrad.md section 7: both sides carry a fixed cost of about the same size (the reduction of
+// splits * n * 9 * c fp32 here, a zero-fill and two casts there), so it is kernel against solver, and the kernel -- a prologue
+// whose loads nothing hides, 144 KB of partial tile per workgroup to store -- needs work to spread those over.  At stride 1 it
+// won at every measured shape with kC3PreferPixels output pixels per split (three full rasters) or more, which came with
+// kC3PreferSteps steps per workgroup or more; with 196 - 224 pixels (2 - 4 steps) the two sides were level, below that the
+// solver won.  At stride 2, where the loader fetches only the first pass of the X raster ahead, no class won measurably.
+constexpr int kC3PreferSteps = 4, kC3PreferPixels = 384;
+int conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int s) {
+  const C3Plan p = c3_plan(b, c, n, h, w, s);
+  if (!p.ok) return MRLA_EUNSUPPORTED;
+  const long long steps = (long long)((p.rows_per_split + p.rmax - 1) / p.rmax) * p.nseg;
+  const long long pixels = (long long)p.rows_per_split * p.wo;
+  return s == 1 && steps >= kC3PreferSteps && pixels >= kC3PreferPixels;
 }
 
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,

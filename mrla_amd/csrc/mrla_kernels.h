@@ -229,6 +229,7 @@ int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, in
 // products over padded rasters of one image's rows (bf16 or fp16); part [rows][n][9][c]
 int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
+int conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int s);
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
                          int s, int dtype, hipStream_t st);
 // conv3x3_fwd.hip -- the forward of that convolution as an implicit GEMM (bf16 or fp16), y [b,ho,wo,n] from x [b,h,w,c] and

@@ -100,11 +100,27 @@ CONV3X3_WGRAD = False   # the weight gradient of an eligible 3x3 convolution (co
 #                         bit-reproducible, and right under graph replay at the small batches where the stock library's
 #                         split-K solver is not -- written straight as the fp32 master weight's gradient.  Forward and input
 #                         gradient stay the stock operator's.  False (the default): conv(x) itself, the very same autograd
-#                         graph and launches as before; conv3x3_wgrad() turns it on for a block of code.
-#                         profiles/conv3x3_wgrad.md has the numbers a change of the default rests on.
+#                         graph and launches as before; conv3x3_wgrad() turns it on for a block of code: EVERYWHERE the
+#                         kernel applies, also where it is the slower one (stride 2, small batches).
+#                         profiles/conv3x3_wgrad.md has the numbers.
 
 
 conv3x3_wgrad = _switch("CONV3X3_WGRAD", "conv3x3_wgrad")
+
+
+CONV3X3_WGRAD_AUTO = True   # the same route by shape: an eligible 3x3 convolution takes its weight gradient from
+#                             mrla_conv3x3_wgrad where the library expects it to take less device time than everything the
+#                             stock operator launches for that gradient (mrla_conv3x3_wgrad_preferred: a rule in the planner's
+#                             quantities, derived in profiles/conv3x3_wgrad.md section 7 -- the stride-1 convolutions of a
+#                             large-batch step; no stride-2 one, nothing at batch 8 / 16).  What changes numerically at a
+#                             routed shape: the gradient is bit-reproducible, and an fp32 master weight receives the fp32 sums
+#                             where the stock path hands back a bf16-rounded gradient (1.7e-3 relative L2 apart:
+#                             tests/test_conv3x3_route_gpu.py).  Everything else -- and every shape with this switch and
+#                             CONV3X3_WGRAD off -- is conv(x) itself, the same autograd graph and launches as before;
+#                             conv3x3_wgrad_auto(False) turns it off for a block of code.
+
+
+conv3x3_wgrad_auto = _switch("CONV3X3_WGRAD_AUTO", "conv3x3_wgrad_auto")
 
 
 CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_applies: the bottleneck's conv2, both of the basic
@@ -2143,6 +2159,24 @@ def conv3x3_applies(conv, x):
     return L.load().mrla_conv3x3_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
 
 
+_WGRAD_PREFERRED = {}      # (b, c, n, h, w, stride, dtype code) -> mrla_conv3x3_wgrad_preferred(...) == 1
+
+
+def _conv3x3_own_wgrad(conv, x):
+    """Whether the weight gradient of `conv(x)` comes from mrla_conv3x3_wgrad: conv3x3_applies, and CONV3X3_WGRAD (everywhere
+    the kernel applies) or CONV3X3_WGRAD_AUTO at a shape the library prefers its own kernel at (asked once per shape)."""
+    if not ((CONV3X3_WGRAD or CONV3X3_WGRAD_AUTO) and conv3x3_applies(conv, x)):
+        return False
+    if CONV3X3_WGRAD:
+        return True
+    b, c, h, w = x.shape
+    key = (b, c, conv.out_channels, h, w, conv.stride[0], _DT[_conv_compute_dtype(x)])
+    hit = _WGRAD_PREFERRED.get(key)
+    if hit is None:
+        hit = _WGRAD_PREFERRED[key] = L.load().mrla_conv3x3_wgrad_preferred(*key) == 1
+    return hit
+
+
 def _own_dgrad_s2(dy, x, w16):
     """dX of a stride-2 3x3 convolution from mrla_conv3x3_dgrad_s2 on dy and the forward's own weight `w16` (channels_last
     [n, c, 3, 3] = [n, 3, 3, c] in memory, 16-byte aligned)."""
@@ -2155,7 +2189,7 @@ def _own_dgrad_s2(dy, x, w16):
 
 class _Conv3x3Fn(torch.autograd.Function):
     """y = conv2d(x, w, stride, padding 1) of a channels_last bf16 or fp16 `x` by the stock operator, on `w` cast to x's dtype as
-    autocast casts it.  Backward: dW [n, 3, 3, c] from mrla_conv3x3_wgrad where `own_wgrad` (CONV3X3_WGRAD and conv3x3_applies
+    autocast casts it.  Backward: dW [n, 3, 3, c] from mrla_conv3x3_wgrad where `own_wgrad` (_conv3x3_own_wgrad
     at the call), in the weight's own dtype -- for an fp32 master weight the fp32 sums themselves, no 16-bit rounding and no
     cast kernel -- returned as [n, c, 3, 3]; dX from mrla_conv3x3_dgrad_s2 where `own_dgrad` (CONV3X3_DGRAD and
     conv3x3_dgrad_applies at the call); what is left from the stock operator's backward, masked to exactly that (its split-K
@@ -2220,7 +2254,7 @@ class _Conv3x3FwdFn(torch.autograd.Function):
     `moments`, else empty.  Backward: dX at stride 1 from the same entry point on dy and the flipped, transposed weight (a
     pure permutation), at stride 2 from mrla_conv3x3_dgrad_s2 on dy and the saved weight itself where `own_dgrad`
     (CONV3X3_DGRAD and conv3x3_dgrad_applies at the call), else from the stock operator's backward; dW from
-    mrla_conv3x3_wgrad where `own_wgrad` (CONV3X3_WGRAD and conv3x3_applies at the call), else from the stock backward --
+    mrla_conv3x3_wgrad where `own_wgrad` (_conv3x3_own_wgrad at the call), else from the stock backward --
     each masked to what is asked for."""
 
     @staticmethod
@@ -2275,18 +2309,19 @@ class _Conv3x3FwdFn(torch.autograd.Function):
 def _conv3x3_own(x, conv, moments):
     dt = _conv_compute_dtype(x)
     return _Conv3x3FwdFn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], moments,
-                               CONV3X3_WGRAD and conv3x3_applies(conv, x), CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x))
+                               _conv3x3_own_wgrad(conv, x), CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x))
 
 
 def conv3x3(x, conv):
     """conv(x) for the 3x3 convolutions of the blocks (resnet_mrla_light.py: conv2 of the bottleneck, both of the basic
     block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, where
-    neither CONV3X3_WGRAD with conv3x3_applies nor CONV3X3_DGRAD with conv3x3_dgrad_applies holds, it IS conv(x): the same
+    neither the own weight gradient (conv3x3_applies, and CONV3X3_WGRAD or CONV3X3_WGRAD_AUTO at a shape
+    mrla_conv3x3_wgrad_preferred answers 1 for) nor CONV3X3_DGRAD with conv3x3_dgrad_applies holds, it IS conv(x): the same
     autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn) whose forward is the stock operator's, whose weight
     gradient is mrla_conv3x3_wgrad's under the first and whose input gradient is mrla_conv3x3_dgrad_s2's under the second."""
     if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
         return _conv3x3_own(x, conv, False)[0]
-    own_wgrad = CONV3X3_WGRAD and conv3x3_applies(conv, x)
+    own_wgrad = _conv3x3_own_wgrad(conv, x)
     own_dgrad = CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x)
     if not (own_wgrad or own_dgrad):
         return conv(x)
