@@ -181,62 +181,54 @@ def check(rc, what):
         raise MrlaHipError(f"{what}: {_ERR.get(rc, 'error')} (code {rc})")
 
 
+def _plan(entry, count, *args):
+    """The `count` integers `entry` answers for the integer arguments `args` (a dtype among them: bf16 if None), or None."""
+    out = (ctypes.c_int * count)()
+    rc = getattr(load(), entry)(*(BF16 if a is None else a for a in args), ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out) if rc == OK else None
+
+
 def conv1x1_plan(m, k, n, addend=False, dtype=None):
     """(pixel blocks per workgroup, pipeline depth, workgroups, moment rows) of mrla_conv1x1_fwd[_add], or None."""
-    out = (ctypes.c_int * 4)()
-    rc = load().mrla_conv1x1_plan(m, k, n, BF16 if dtype is None else dtype, int(addend), ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _plan("mrla_conv1x1_plan", 4, m, k, n, dtype, int(addend))
 
 
 def conv1x1_f32_plan(m, k, n):
     """(kernel form, X chunks in flight, workgroups, moment rows) of mrla_conv1x1_f32_fwd, or None."""
-    out = (ctypes.c_int * 4)()
-    rc = load().mrla_conv1x1_f32_plan(m, k, n, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _plan("mrla_conv1x1_f32_plan", 4, m, k, n)
 
 
 def conv1x1_wgrad_plan(m, k, n, dtype=None):
     """(chunks per workgroup, LDS stages, tile n, tile k, splits, tiles) of mrla_conv1x1_wgrad, or None."""
-    out = (ctypes.c_int * 6)()
-    rc = load().mrla_conv1x1_wgrad_plan(m, k, n, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
-
-
-def _spatial_plan(entry, count, shape, dtype):
-    """The `count` integers `entry` answers for the integers `shape` and the dtype (bf16 if None), or None."""
-    out = (ctypes.c_int * count)()
-    rc = getattr(load(), entry)(*shape, BF16 if dtype is None else dtype, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _plan("mrla_conv1x1_wgrad_plan", 6, m, k, n, dtype)
 
 
 def conv3x3_wgrad_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_wgrad, or None."""
-    return _spatial_plan("mrla_conv3x3_wgrad_plan", 6, (b, c, n, h, w, stride), dtype)
+    return _plan("mrla_conv3x3_wgrad_plan", 6, b, c, n, h, w, stride, dtype)
 
 
 def conv3x3_fwd_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, output rows per workgroup, rows per step, segments per row, record rows, workgroups) of mrla_conv3x3_fwd, or
     None."""
-    return _spatial_plan("mrla_conv3x3_fwd_plan", 6, (b, c, n, h, w, stride), dtype)
+    return _plan("mrla_conv3x3_fwd_plan", 6, b, c, n, h, w, stride, dtype)
 
 
 def conv3x3_dgrad_s2_plan(b, c, n, h, w, dtype=None):
     """(tile c, cell rows per workgroup range, cell rows per step, segments per row, ranges, workgroups) of
     mrla_conv3x3_dgrad_s2, or None."""
-    return _spatial_plan("mrla_conv3x3_dgrad_s2_plan", 6, (b, c, n, h, w), dtype)
+    return _plan("mrla_conv3x3_dgrad_s2_plan", 6, b, c, n, h, w, dtype)
 
 
 def stem_conv_wgrad_plan(b, n, h, w, dtype=None):
     """(tile n, output rows per split, splits, column segments per row, LDS bytes, output columns per segment, output rows
     per step) of mrla_stem_conv_wgrad, or None."""
-    return _spatial_plan("mrla_stem_conv_wgrad_plan", 7, (b, n, h, w), dtype)
+    return _plan("mrla_stem_conv_wgrad_plan", 7, b, n, h, w, dtype)
 
 
 def bn_pool_plan(b, c, h, w, dtype, band=0):
     """(Ho, Wo, row bands per image, waves per workgroup, ho0, ho1 of `band`) of the mrla_bn_relu_pool_* passes, or None."""
-    out = (ctypes.c_int * 6)()
-    rc = load().mrla_bn_pool_plan(b, c, h, w, dtype, NHWC, band, ctypes.cast(out, ctypes.c_void_p))
-    return tuple(out) if rc == OK else None
+    return _plan("mrla_bn_pool_plan", 6, b, c, h, w, dtype, NHWC, band)
 
 
 def call(name, *args):

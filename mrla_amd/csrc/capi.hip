@@ -669,40 +669,59 @@ int mrla_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, const 
   return launch_bn_relu_pool_bwd(dp, x, sc, sh, cb, dx, b, c, h, w, dtype, (hipStream_t)stream);
 }
 
-int mrla_conv1x1_rows(int m, int k, int n, int dtype) {
+// The 16-bit 1x1 GEMMs (conv1x1*.hip).  One argument check for the queries and the launches of a shape, as conv3x3_args below:
+// bad extents or a dtype code that is none are MRLA_EINVAL, fp32 (which has entry points of its own) MRLA_EUNSUPPORTED.
+// Every entry tests its pointers and its other arguments for MRLA_EINVAL in front of it.
+static int conv1x1_args(int m, int k, int n, int dtype) {
   if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_rows(m, k, n);
+  return MRLA_OK;
+}
+
+// ... of a weight gradient: dw is of the operands' type or fp32 -- a bf16 gradient of fp16 operands (or the reverse) is a
+// caller's mistake, and reported as one in front of an unsupported operand type
+static int conv1x1_wgrad_args(int m, int k, int n, int dtype, int dw_dtype) {
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc == MRLA_EINVAL) return rc;
+  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
+  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
+  return rc;
+}
+
+int mrla_conv1x1_rows(int m, int k, int n, int dtype) {
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_rows(m, k, n);
 }
 
 int mrla_conv1x1_plan(int m, int k, int n, int dtype, int addend, int* out) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || !out) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_plan(m, k, n, addend, out);
+  if (!out) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_plan(m, k, n, addend, out);
 }
 
 int mrla_conv1x1_wgrad_plan(int m, int k, int n, int dtype, int* out) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || !out) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_wgrad_plan(m, k, n, out);
+  if (!out) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_wgrad_plan(m, k, n, out);
 }
 
 int mrla_conv1x1_fwd(const void* x, const void* w, void* y, float* mom_part, int m, int k, int n, int dtype, void* stream) {
-  if (!x || !w || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!x || !w || !y) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc != MRLA_OK) return rc;
   return launch_conv1x1_fwd(x, w, y, mom_part, m, k, n, dtype, (hipStream_t)stream);
 }
 
 int mrla_conv1x1_add_supported(int m, int k, int n, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_wide_rows(m, k, n) > 0 ? 1 : MRLA_EUNSUPPORTED;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_wide_rows(m, k, n) > 0 ? 1 : MRLA_EUNSUPPORTED;
 }
 
 int mrla_conv1x1_fwd_add(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int dtype,
                          void* stream) {
-  if (!x || !w || !addend || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!x || !w || !addend || !y) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc != MRLA_OK) return rc;
   return launch_conv1x1_wide(x, w, addend, y, nullptr, m, k, n, dtype, (hipStream_t)stream);
 }
 
@@ -711,48 +730,45 @@ static bool bad_addend_geometry(int m, int b, int h, int w, int sh, int sw) {
 }
 
 int mrla_conv1x1_addend_supported(int m, int k, int n, int sh, int sw, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || sh <= 0 || sw <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (sh <= 0 || sw <= 0) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc != MRLA_OK) return rc;
   return conv1x1_addend_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
 }
 
 int mrla_conv1x1_fwd_addend(const void* x, const void* w, const void* addend, void* y, int m, int k, int n, int b, int h,
                             int w_, int sh, int sw, int dtype, void* stream) {
-  if (!x || !w || !addend || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || bad_addend_geometry(m, b, h, w_, sh, sw))
-    return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!x || !w || !addend || !y || bad_addend_geometry(m, b, h, w_, sh, sw)) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc != MRLA_OK) return rc;
   return launch_conv1x1_addend(x, w, addend, y, m, k, n, b, h, w_, sh, sw, dtype, (hipStream_t)stream);
 }
 
 int mrla_conv1x1_fwd_affine_supported(int m, int k, int n, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_affine_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_affine_supported(m, k, n) ? 1 : MRLA_EUNSUPPORTED;
 }
 
 int mrla_conv1x1_fwd_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int m, int k,
                             int n, int dtype, void* stream) {
-  if (!x || !w || !sc || !sh || !y || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype) || (relu != 0 && relu != 1))
-    return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!x || !w || !sc || !sh || !y || (relu != 0 && relu != 1)) return MRLA_EINVAL;
+  const int rc = conv1x1_args(m, k, n, dtype);
+  if (rc != MRLA_OK) return rc;
   if (!conv1x1_affine_supported(m, k, n)) return MRLA_EUNSUPPORTED;
   if (((uintptr_t)sc | (uintptr_t)sh) & 15) return MRLA_EINVAL;      // a thread reads 4 or 8 channels of sc, sh as 16-byte vectors
   return launch_conv1x1_affine(x, w, sc, sh, relu, y, m, k, n, dtype, (hipStream_t)stream);
 }
 
 int mrla_conv1x1_wgrad_rows(int m, int k, int n, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_wgrad_rows(m, k, n);
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_wgrad_rows(m, k, n);
 }
 
 int mrla_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                        void* stream) {
-  if (!dy || !x || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  // dw is of the operands' type or fp32: a bf16 gradient of fp16 operands (or the reverse) is a caller's mistake
-  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
+  const int rc = conv1x1_wgrad_args(m, k, n, dtype, dw_dtype);
+  if (rc != MRLA_OK) return rc;
   return launch_conv1x1_wgrad(dy, x, part, dw, dw_dtype == MRLA_F32, m, k, n, dtype, (hipStream_t)stream);
 }
 
@@ -886,19 +902,16 @@ int mrla_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* 
 }
 
 int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_wgrad_bn_supported(m, k, n);
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_wgrad_bn_supported(m, k, n);
 }
 
 int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
                           void* dy_out, const void* x, float* part, void* dw, int m, int k, int n, int dtype, int dw_dtype,
                           void* stream) {
-  if (!g || !xb || !sc || !sh || !cb || !dy_out || !x || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype))
-    return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!g || !xb || !sc || !sh || !cb || !dy_out || !x || !part || !dw) return MRLA_EINVAL;
+  const int rc = conv1x1_wgrad_args(m, k, n, dtype, dw_dtype);
+  if (rc != MRLA_OK) return rc;
   // a lane reads 8 channels of sc, sh and 24 floats of cb as float4; dy_out is written while g and xb are still read
   if (((uintptr_t)sc | (uintptr_t)sh | (uintptr_t)cb) & 15) return MRLA_EINVAL;
   if (dy_out == g || dy_out == xb) return MRLA_EINVAL;
@@ -907,19 +920,16 @@ int mrla_conv1x1_wgrad_bn(const void* g, const void* xb, const float* sc, const 
 }
 
 int mrla_conv1x1_wgrad_bn_dx_supported(int m, int k, int n, int dtype) {
-  if (m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  return conv1x1_wgrad_bn_dx_supported(m, k, n);
+  const int rc = conv1x1_args(m, k, n, dtype);
+  return rc != MRLA_OK ? rc : conv1x1_wgrad_bn_dx_supported(m, k, n);
 }
 
 int mrla_conv1x1_wgrad_bn_dx(const void* g, const void* xb, const float* sc, const float* sh, const float* cb, int relu,
                              const void* x, const void* wt, void* dx, float* part, void* dw, int m, int k, int n, int dtype,
                              int dw_dtype, void* stream) {
-  if (!g || !xb || !sc || !sh || !cb || !x || !wt || !dx || !part || !dw || m <= 0 || k <= 0 || n <= 0 || bad_dtype(dtype))
-    return MRLA_EINVAL;
-  if (dw_dtype != MRLA_BF16 && dw_dtype != MRLA_F16 && dw_dtype != MRLA_F32) return MRLA_EINVAL;
-  if ((dw_dtype == MRLA_F16 && dtype != MRLA_F16) || (dw_dtype == MRLA_BF16 && dtype == MRLA_F16)) return MRLA_EINVAL;
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  if (!g || !xb || !sc || !sh || !cb || !x || !wt || !dx || !part || !dw) return MRLA_EINVAL;
+  const int rc = conv1x1_wgrad_args(m, k, n, dtype, dw_dtype);
+  if (rc != MRLA_OK) return rc;
   // as mrla_conv1x1_wgrad_bn; a lane reads 16 bytes of a row of wt and stores 16 bytes of a row of dx
   if (((uintptr_t)sc | (uintptr_t)sh | (uintptr_t)cb | (uintptr_t)wt | (uintptr_t)dx) & 15) return MRLA_EINVAL;
   if (dx == g || dx == xb || dx == x) return MRLA_EINVAL;      // dx is written while g, xb and x are still read

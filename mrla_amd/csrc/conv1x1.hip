@@ -32,6 +32,7 @@
 
 #include "conv1x1_addend.h"
 #include "conv1x1_affine.h"
+#include "conv1x1_lds.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -334,31 +335,44 @@ static bool conv1x1_geo(GemmGeo* g, int M, int K, int N) {
   // the partial buffer with zero rows up to the next divisor of M
   for (int t = gx; t >= std::max(1, gx - gx / 4); --t)
     if (M % t == 0) { gx = t; break; }
-  int rows = gx;
-  while (rows <= 2 * gx + 64 && M % rows) ++rows;
-  if (M % rows) return false;
+  const int rows = pad_rows_to_divisor(M, gx);
+  if (!rows) return false;
   g->gx = gx;
   g->rows = rows;
   return true;
 }
 
+// The kernel form of a shape, asked in this order: the streaming kernel of conv1x1_wide.hip (N % 256 == 0), the narrow kernel
+// of this file (*g: its geometry), the K-streaming kernel of conv1x1_kstream.hip (K >= 512)
+enum class Form { none, wide, narrow, kstream };
+
+static Form conv1x1_form(int M, int K, int N, GemmGeo* g) {
+  if (conv1x1_wide_rows(M, K, N) > 0) return Form::wide;
+  if (conv1x1_geo(g, M, K, N)) return Form::narrow;
+  return conv1x1_kstream_supported(M, K, N) ? Form::kstream : Form::none;
+}
+
 int conv1x1_rows(int M, int K, int N) {
-  const int wide = conv1x1_wide_rows(M, K, N);                 // N % 256 == 0: the streaming kernel of conv1x1_wide.hip
-  if (wide > 0) return wide;
   GemmGeo g;
-  if (conv1x1_geo(&g, M, K, N)) return g.rows;
-  return conv1x1_kstream_supported(M, K, N) ? conv1x1_kstream_rows(M, K, N) : MRLA_EUNSUPPORTED;   // K >= 512: one record row per pixel tile
+  switch (conv1x1_form(M, K, N, &g)) {
+    case Form::wide: return conv1x1_wide_rows(M, K, N);
+    case Form::narrow: return g.rows;
+    case Form::kstream: return conv1x1_kstream_rows(M, K, N);      // one record row per pixel tile
+    default: return MRLA_EUNSUPPORTED;
+  }
 }
 
 // {32-pixel blocks per workgroup (wide form) / per pixel-wave (narrow form), pipeline depth in blocks, workgroups, rows}
+// add: the fp32 addend of mrla_conv1x1_fwd_add, which only the wide form has
 int conv1x1_plan(int M, int K, int N, int add, int* out) {
-  if (conv1x1_wide_plan(M, K, N, add, out) == MRLA_OK) return MRLA_OK;
   GemmGeo g;
-  if (!add && !conv1x1_geo(&g, M, K, N) && conv1x1_kstream_supported(M, K, N)) {
+  const Form form = conv1x1_form(M, K, N, &g);
+  if (form == Form::wide) return conv1x1_wide_plan(M, K, N, add, out);
+  if (add || form == Form::none) return MRLA_EUNSUPPORTED;
+  if (form == Form::kstream) {
     out[0] = K / 32; out[1] = conv1x1_kstream_stages(M, K, N); out[2] = 0; out[3] = conv1x1_kstream_rows(M, K, N);   // 32-deep chunks per tile, LDS stages, -, record rows
     return MRLA_OK;
   }
-  if (add || !conv1x1_geo(&g, M, K, N)) return MRLA_EUNSUPPORTED;
   const int nblk = (M + 31) / 32;
   out[0] = (nblk + g.gx * g.WM - 1) / (g.gx * g.WM);
   out[1] = 2;                               // the next block's X fragments are fetched during this block's MFMAs
@@ -367,48 +381,41 @@ int conv1x1_plan(int M, int K, int N, int add, int* out) {
   return MRLA_OK;
 }
 
-int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st) {
-  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  if (conv1x1_wide_rows(M, K, N) > 0) return launch_conv1x1_wide(x, w, nullptr, y, part, M, K, N, dtype, st);
-  GemmGeo g;
-  if (!conv1x1_geo(&g, M, K, N)) {
-    if (!conv1x1_kstream_supported(M, K, N)) return MRLA_EUNSUPPORTED;
-    return launch_conv1x1_kstream(x, w, y, part, M, K, N, dtype, st);
-  }
-  const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
-#define CALL_T(KERNEL, T, KS, MO, NWV)                                                                             \
-  {                                                                                                                  \
-    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, MO, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;        \
-    hipLaunchKernelGGL((KERNEL<KS, MO, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, (T*)y, part, M, N,    \
-                       g.NS, g.WN, g.rows);                                                                          \
-  }
-#define CALL_W(KS, MO, NWV)                                                                                          \
-  {                                                                                                                  \
-    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_kernel, f16_t, KS, MO, NWV)                                        \
-    else CALL_T(conv1x1_fwd_kernel, bf16_t, KS, MO, NWV)                                                             \
-  }
-#define CALL_M(KS, MO) { if (g.NW == 4) CALL_W(KS, MO, 4) else CALL_W(KS, MO, 8) }
-#define CALL(KS) { if (part) CALL_M(KS, true) else CALL_M(KS, false) }
+// The narrow instance of a geometry: f(KS, NW) with both as integral constants.  conv1x1_geo() takes eight waves at K = 256:
+// no four-wave instance there.
+template <typename F>
+static int narrow_instance(int K, int NW, F&& f) {
   switch (K) {
-    case 64:  CALL(4) break;
-    case 128: CALL(8) break;
-    case 256:                               // conv1x1_geo() takes eight waves at K = 256: no four-wave instance
-      if (g.NW != 8) return MRLA_EUNSUPPORTED;
-      if (part) CALL_W(16, true, 8) else CALL_W(16, false, 8)
-      break;
+    case 64: return NW == 4 ? f(Int<4>(), Int<4>()) : f(Int<4>(), Int<8>());
+    case 128: return NW == 4 ? f(Int<8>(), Int<4>()) : f(Int<8>(), Int<8>());
+    case 256: return NW == 8 ? f(Int<16>(), Int<8>()) : MRLA_EUNSUPPORTED;
     default: return MRLA_EUNSUPPORTED;
   }
-#undef CALL
-#undef CALL_M
-#undef CALL_W
-#undef CALL_T
-  return hip_status(hipGetLastError());
+}
+
+int launch_conv1x1_fwd(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st) {
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  GemmGeo g;
+  switch (conv1x1_form(M, K, N, &g)) {
+    case Form::wide: return launch_conv1x1_wide(x, w, nullptr, y, part, M, K, N, dtype, st);
+    case Form::kstream: return launch_conv1x1_kstream(x, w, y, part, M, K, N, dtype, st);
+    case Form::none: return MRLA_EUNSUPPORTED;
+    case Form::narrow: break;
+  }
+  const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
+  return narrow_instance(K, g.NW, [&](auto ks, auto nw) {
+    constexpr int KS = decltype(ks)::value, NW = decltype(nw)::value;
+    return part ? launch_by_dtype(dtype, conv1x1_fwd_kernel<KS, true, NW>, conv1x1_fwd_f16_kernel<KS, true, NW>, grid, block,
+                                  g.lds, st, x, w, y, part, M, N, g.NS, g.WN, g.rows)
+                : launch_by_dtype(dtype, conv1x1_fwd_kernel<KS, false, NW>, conv1x1_fwd_f16_kernel<KS, false, NW>, grid, block,
+                                  g.lds, st, x, w, y, part, M, N, g.NS, g.WN, g.rows);
+  });
 }
 
 int conv1x1_addend_supported(int M, int K, int N) {
   if ((size_t)M * std::max(N, K) * 2 >= (size_t)1 << 31) return 0;      // (also keeps every pixel index exact in fp32)
   GemmGeo g;
-  return conv1x1_wide_rows(M, K, N) > 0 || conv1x1_geo(&g, M, K, N) || conv1x1_kstream_supported(M, K, N);
+  return conv1x1_form(M, K, N, &g) != Form::none;
 }
 
 // The same dispatch as launch_conv1x1_fwd, with the addend (conv1x1_addend.h; sh = sw = 1: as large as y).  The wide form
@@ -417,79 +424,47 @@ int launch_conv1x1_addend(const void* x, const void* w, const void* addend, void
                           int sh, int sw, int dtype, hipStream_t st) {
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   if (!conv1x1_addend_supported(M, K, N)) return MRLA_EUNSUPPORTED;
-  if (conv1x1_wide_rows(M, K, N) > 0)
-    return sh * sw == 1 ? launch_conv1x1_wide(x, w, addend, y, nullptr, M, K, N, dtype, st)
-                        : launch_conv1x1_wide_sparse(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
   GemmGeo g;
-  if (!conv1x1_geo(&g, M, K, N)) return launch_conv1x1_kstream_addend(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
+  switch (conv1x1_form(M, K, N, &g)) {
+    case Form::wide:
+      return sh * sw == 1 ? launch_conv1x1_wide(x, w, addend, y, nullptr, M, K, N, dtype, st)
+                          : launch_conv1x1_wide_sparse(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
+    case Form::kstream: return launch_conv1x1_kstream_addend(x, w, addend, y, M, K, N, b, h, wd, sh, sw, dtype, st);
+    case Form::none: return MRLA_EUNSUPPORTED;
+    case Form::narrow: break;
+  }
   const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
   const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
-#define CALL_T(KERNEL, T, KS, NWV)                                                                                    \
-  {                                                                                                                   \
-    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;             \
-    hipLaunchKernelGGL((KERNEL<KS, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, (const T*)addend, (T*)y,   \
-                       M, N, g.NS, g.WN, ag);                                                                         \
-  }
-#define CALL_W(KS, NWV)                                                                                               \
-  {                                                                                                                   \
-    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_addend_kernel, f16_t, KS, NWV)                                      \
-    else CALL_T(conv1x1_fwd_addend_kernel, bf16_t, KS, NWV)                                                           \
-  }
-#define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
-  switch (K) {
-    case 64:  CALL(4) break;
-    case 128: CALL(8) break;
-    case 256:
-      if (g.NW != 8) return MRLA_EUNSUPPORTED;
-      CALL_W(16, 8)
-      break;
-    default: return MRLA_EUNSUPPORTED;
-  }
-#undef CALL
-#undef CALL_W
-#undef CALL_T
-  return hip_status(hipGetLastError());
+  return narrow_instance(K, g.NW, [&](auto ks, auto nw) {
+    constexpr int KS = decltype(ks)::value, NW = decltype(nw)::value;
+    return launch_by_dtype(dtype, conv1x1_fwd_addend_kernel<KS, NW>, conv1x1_fwd_f16_addend_kernel<KS, NW>, grid, block, g.lds,
+                           st, x, w, addend, y, M, N, g.NS, g.WN, ag);
+  });
 }
 
 // The same dispatch as launch_conv1x1_fwd (same planners, grids and LDS sizes) with the eval-mode BatchNorm's affine
 // (+ReLU) applied to the rounded product on its way out (conv1x1_affine.h).  No moment records.
-int conv1x1_affine_supported(int M, int K, int N) { return conv1x1_rows(M, K, N) > 0; }
+int conv1x1_affine_supported(int M, int K, int N) {
+  GemmGeo g;
+  return conv1x1_form(M, K, N, &g) != Form::none;
+}
 
 int launch_conv1x1_affine(const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M, int K,
                           int N, int dtype, hipStream_t st) {
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
-  if (conv1x1_wide_rows(M, K, N) > 0) return launch_conv1x1_wide_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
   GemmGeo g;
-  if (!conv1x1_geo(&g, M, K, N)) {
-    if (!conv1x1_kstream_supported(M, K, N)) return MRLA_EUNSUPPORTED;
-    return launch_conv1x1_kstream_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  switch (conv1x1_form(M, K, N, &g)) {
+    case Form::wide: return launch_conv1x1_wide_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
+    case Form::kstream: return launch_conv1x1_kstream_affine(x, w, sc, sh, relu, y, M, K, N, dtype, st);
+    case Form::none: return MRLA_EUNSUPPORTED;
+    case Form::narrow: break;
   }
   const dim3 grid(g.gx, g.gy), block(g.NW * kWave);
-#define CALL_T(KERNEL, T, KS, NWV)                                                                                    \
-  {                                                                                                                   \
-    if (lds_opt_in(reinterpret_cast<const void*>(KERNEL<KS, NWV>), g.lds) != hipSuccess) return MRLA_EHIP;             \
-    hipLaunchKernelGGL((KERNEL<KS, NWV>), grid, block, g.lds, st, (const T*)x, (const T*)w, sc, sh, relu, (T*)y, M, N, \
-                       g.NS, g.WN);                                                                                   \
-  }
-#define CALL_W(KS, NWV)                                                                                               \
-  {                                                                                                                   \
-    if (dtype == MRLA_F16) CALL_T(conv1x1_fwd_f16_affine_kernel, f16_t, KS, NWV)                                      \
-    else CALL_T(conv1x1_fwd_affine_kernel, bf16_t, KS, NWV)                                                           \
-  }
-#define CALL(KS) { if (g.NW == 4) CALL_W(KS, 4) else CALL_W(KS, 8) }
-  switch (K) {
-    case 64:  CALL(4) break;
-    case 128: CALL(8) break;
-    case 256:
-      if (g.NW != 8) return MRLA_EUNSUPPORTED;
-      CALL_W(16, 8)
-      break;
-    default: return MRLA_EUNSUPPORTED;
-  }
-#undef CALL
-#undef CALL_W
-#undef CALL_T
-  return hip_status(hipGetLastError());
+  return narrow_instance(K, g.NW, [&](auto ks, auto nw) {
+    constexpr int KS = decltype(ks)::value, NW = decltype(nw)::value;
+    return launch_by_dtype(dtype, conv1x1_fwd_affine_kernel<KS, NW>, conv1x1_fwd_f16_affine_kernel<KS, NW>, grid, block, g.lds,
+                           st, x, w, sc, sh, relu, y, M, N, g.NS, g.WN);
+  });
 }
 
 }  // namespace mrla

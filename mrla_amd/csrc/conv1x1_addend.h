@@ -54,7 +54,7 @@ __device__ __forceinline__ int addend_row(const AddendGeo& g, int p, int M) {
 // back to back.  (rows * N * 2 < 2^31: conv1x1_addend_supported.)
 template <typename T>
 __device__ __forceinline__ auto addend_rsrc(const T* A, const AddendGeo& g, int N) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A), 0, (int)((size_t)g.rows * N * 2), 0x00020000);
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(A), 0, (int)((size_t)g.rows * N * 2), kBufFlags);
 }
 __device__ __forceinline__ unsigned addend_offset(const AddendGeo& g, int p, int M, int N, int col) {
   const int row = addend_row(g, p, M);

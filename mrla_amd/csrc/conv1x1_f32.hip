@@ -34,6 +34,7 @@
 // operand's lines hit in the vector cache), and each workgroup writes its partial tiles of part[split]; fixed split, no atomics.
 #include <algorithm>
 
+#include "conv1x1_lds.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -384,20 +385,15 @@ int launch_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y
   F32Geo g;
   if (!f32_geo(&g, M, K, N)) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.gx, g.gy), block(kFWaves * kWave);
-#define CALL_K(WNV, MO, STR)                                                                                              \
-  {                                                                                                                       \
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_f32_fwd_kernel<WNV, MO, STR>), g.lds) != hipSuccess) return MRLA_EHIP; \
-    hipLaunchKernelGGL((conv1x1_f32_fwd_kernel<WNV, MO, STR>), grid, block, g.lds, st, x, w, y, part, M, K, N, w_trans);   \
-  }
-#define CALL_M(WNV, STR) { if (part) CALL_K(WNV, true, STR) else CALL_K(WNV, false, STR) }
-  if (g.stream) {
-    if (g.WN == 2) CALL_M(2, true) else CALL_M(1, true)
-  } else {
-    if (g.WN == 4) CALL_M(4, false) else if (g.WN == 2) CALL_M(2, false) else CALL_M(1, false)
-  }
-#undef CALL_M
-#undef CALL_K
-  return hip_status(hipGetLastError());
+  auto launch = [&](auto wn, auto stream) {
+    constexpr int WN = decltype(wn)::value;
+    constexpr bool STREAM = decltype(stream)::value;
+    return part ? launch_kernel(conv1x1_f32_fwd_kernel<WN, true, STREAM>, grid, block, g.lds, st, x, w, y, part, M, K, N, w_trans)
+                : launch_kernel(conv1x1_f32_fwd_kernel<WN, false, STREAM>, grid, block, g.lds, st, x, w, y, part, M, K, N, w_trans);
+  };
+  if (g.stream) return g.WN == 2 ? launch(Int<2>(), std::true_type()) : launch(Int<1>(), std::true_type());
+  return g.WN == 4 ? launch(Int<4>(), std::false_type())
+                   : g.WN == 2 ? launch(Int<2>(), std::false_type()) : launch(Int<1>(), std::false_type());
 }
 
 int conv1x1_f32_wgrad_rows(int M, int K, int N) {
@@ -408,9 +404,9 @@ int conv1x1_f32_wgrad_rows(int M, int K, int N) {
 int launch_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int M, int K, int N, hipStream_t st) {
   const F32WgPlan p = f32_wgrad_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
-  hipLaunchKernelGGL(conv1x1_f32_wgrad_kernel, dim3(p.groups * p.splits), dim3(kFWaves * kWave), 0, st, dy, x, part, M, K, N,
-                     p.chunks_per_wg, p.groups);
-  if (hipGetLastError() != hipSuccess) return MRLA_EHIP;
+  const int rc = launch_kernel(conv1x1_f32_wgrad_kernel, dim3(p.groups * p.splits), dim3(kFWaves * kWave), 0, st, dy, x, part, M,
+                               K, N, p.chunks_per_wg, p.groups);
+  if (rc != MRLA_OK) return rc;
   return launch_conv1x1_wgrad_reduce_f32(part, dw, p.splits, N * K, st);
 }
 

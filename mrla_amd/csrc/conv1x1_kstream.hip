@@ -17,7 +17,7 @@
 //     the other's MFMAs (a K = 512 tile is only 16 chunks long: a lone workgroup would spend a third of its life
 //     filling and draining its pipeline);
 //   * LDS reads are inline asm with explicit lgkmcnt fences, the barrier is a bare s_barrier and the DMA waits are
-//     constant-count vmcnt (see conv1x1_wgrad.hip: the compiler would drain all DMA stages at every LDS access);
+//     constant-count vmcnt (see conv1x1_lds.h: the compiler would drain all DMA stages at every LDS access);
 //   * the inference use behind an eval-mode BatchNorm (the *_affine_kernel entries, AFF; no moments, no addend): the thread
 //     that copies a 16-byte piece out puts it through the BatchNorm's per-channel affine and ReLU (conv1x1_affine.h); it
 //     keeps the same 8 channels for all its rows, and fetches their 8 + 8 coefficients once the accumulation is over;
@@ -29,6 +29,7 @@
 
 #include "conv1x1_addend.h"
 #include "conv1x1_affine.h"
+#include "conv1x1_lds.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -37,7 +38,6 @@ namespace {
 
 typedef c1_f32x16 ks_f32x16;
 
-#define MRLA_KS_FLAGS 0x00020000          /* raw buffer descriptor word 3 (as nhwc_rows.h) */
 constexpr int kKsWaves = 8;
 constexpr int kKsKC = 32;                 // reduction elements per chunk (64-byte rows)
 constexpr int kKsStages = 3;
@@ -54,25 +54,9 @@ struct KsGeo {
   static_assert(ROWS <= 384 && TM * TN * 2 <= kLds - 8192, "stage memory doubles as the output tile");
 };
 
-__device__ __forceinline__ unsigned ks_lds_addr(const void* p) {
-  return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
-}
-__device__ __forceinline__ void ks_read16(u32x4& v, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-}
-__device__ __forceinline__ void ks_write16(unsigned addr, const u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ks_fence(u32x4& v, bool wait) {
-  if (wait) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-  else asm volatile("" : "+v"(v)::"memory");
-}
 __device__ __forceinline__ int ks_swz(int row) { return (row >> 2) & 3; }      // slot swizzle of a 64-byte row
-__device__ __forceinline__ int ks_oswz(int row) { return row & 7; }            // chunk swizzle of an output-tile row
 
-
-// Copy the staged tile [TM][TN] (16-byte chunks swizzled by ks_oswz) out as whole rows; MOM: also the BatchNorm moment
+// Copy the staged tile [TM][TN] (16-byte chunks swizzled by out_swz) out as whole rows; MOM: also the BatchNorm moment
 // record of this pixel tile per channel (MRLA_GEMM_MOMENTS: sum (y - p), sum (y - p)^2, p, count; y = the ROUNDED outputs,
 // p = the tile's first pixel) -- thread (srow, chunk) keeps eight channels over its rows, the RPI row-threads of a chunk are
 // folded through LDS in a fixed order once the tile has been read.
@@ -111,8 +95,8 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
   float piv[8], s1[8], s2[8];
   if (MOM) {
     u32x4 pv;
-    ks_read16(pv, lds0 + ((chunk ^ ks_oswz(0)) << 4));               // tile row 0
-    ks_fence<0>(pv, true);
+    lds_read16(pv, lds0 + ((chunk ^ out_swz(0)) << 4));               // tile row 0
+    lds_fence<0>(pv, true);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const unsigned wv = j == 0 ? pv.x : j == 1 ? pv.y : j == 2 ? pv.z : pv.w;
@@ -125,8 +109,8 @@ __device__ __forceinline__ void ks_store_tile(unsigned char* smem_raw, unsigned 
   for (int i = 0; i < TM / RPI; ++i) {
     const int row = srow + RPI * i;
     u32x4 v;
-    ks_read16(v, lds0 + row * (TN * 2) + ((chunk ^ ks_oswz(row)) << 4));
-    ks_fence<0>(v, true);
+    lds_read16(v, lds0 + row * (TN * 2) + ((chunk ^ out_swz(row)) << 4));
+    lds_fence<0>(v, true);
     if (ADD) v = addend_add8<T>(v, av[i]);
     if (AFF) v = affine8<T>(v, af.sc, af.sh, af.relu);
     if (m0 + row < M) {
@@ -191,8 +175,8 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
 
   // ---- DMA plan: instruction u = wave + 8*i covers stage rows 16u .. 16u+15 (4 lanes per 64-byte row);
   //      rows [0, TM) are X pixels, [TM, TM+TN) W channels, the rest does not exist (out-of-bounds offset: no traffic) ----
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), kBufFlags);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), kBufFlags);
   unsigned voff[kKsNI];
   bool isw[kKsNI];
 #pragma unroll
@@ -216,7 +200,7 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
   };
 
   // ---- operand addresses: A = W rows of this wave's two 32-channel blocks, B = X rows of its PB pixel blocks ----
-  const unsigned lds0 = ks_lds_addr(smem_raw);
+  const unsigned lds0 = lds_addr(smem_raw);
   unsigned offA[2], offB[PB];
   int fA[2], fB[PB];
 #pragma unroll
@@ -256,25 +240,25 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) ks_read16(a[ks][cb], offA[cb] + sbo + (((2 * ks + h) ^ fA[cb]) << 4));
+      for (int cb = 0; cb < 2; ++cb) lds_read16(a[ks][cb], offA[cb] + sbo + (((2 * ks + h) ^ fA[cb]) << 4));
 #pragma unroll
-      for (int p = 0; p < PB; ++p) ks_read16(b[ks][p], offB[p] + sbo + (((2 * ks + h) ^ fB[p]) << 4));
+      for (int p = 0; p < PB; ++p) lds_read16(b[ks][p], offB[p] + sbo + (((2 * ks + h) ^ fB[p]) << 4));
     }
     // k-step 0 is complete when at most the (2 + PB) reads of k-step 1 are outstanding
-    ks_fence<2 + PB>(a[0][0], true);
-    ks_fence<2 + PB>(a[0][1], false);
+    lds_fence<2 + PB>(a[0][0], true);
+    lds_fence<2 + PB>(a[0][1], false);
 #pragma unroll
-    for (int p = 0; p < PB; ++p) ks_fence<2 + PB>(b[0][p], false);
+    for (int p = 0; p < PB; ++p) lds_fence<2 + PB>(b[0][p], false);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int p = 0; p < PB; ++p)
 #pragma unroll
       for (int cb = 0; cb < 2; ++cb)
         E::mfma(acc[p][cb], __builtin_bit_cast(ks_x8, a[0][cb]), __builtin_bit_cast(ks_x8, b[0][p]));
-    ks_fence<0>(a[1][0], true);
-    ks_fence<0>(a[1][1], false);
+    lds_fence<0>(a[1][0], true);
+    lds_fence<0>(a[1][1], false);
 #pragma unroll
-    for (int p = 0; p < PB; ++p) ks_fence<0>(b[1][p], false);
+    for (int p = 0; p < PB; ++p) lds_fence<0>(b[1][p], false);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int p = 0; p < PB; ++p)
@@ -311,8 +295,8 @@ __device__ __forceinline__ void conv1x1_kstream_body(const T* __restrict__ X, co
           q[4 * g + 2 + t] = sw[1];
         }
       const int ch0 = wn * 8 + cb * 4 + h;                     // 16-byte chunk index of channels 32*cb + 8*h .. (+7)
-      ks_write16(orow + (((ch0) ^ ks_oswz(trow)) << 4), (u32x4){q[0], q[1], q[2], q[3]});
-      ks_write16(orow + (((ch0 + 2) ^ ks_oswz(trow)) << 4), (u32x4){q[4], q[5], q[6], q[7]});
+      lds_write16(orow + (((ch0) ^ out_swz(trow)) << 4), (u32x4){q[0], q[1], q[2], q[3]});
+      lds_write16(orow + (((ch0 + 2) ^ out_swz(trow)) << 4), (u32x4){q[4], q[5], q[6], q[7]});
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -401,8 +385,8 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
   const int wn = wave & 3, wm = wave >> 2;
   const int nchunks = K / kKsKC;
 
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_KS_FLAGS);
-  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), MRLA_KS_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), kBufFlags);
+  const auto rsW = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(W), 0, (int)((size_t)N * K * 2), kBufFlags);
   unsigned voff[G::NI];
 #pragma unroll
   for (int i = 0; i < G::NI; ++i) {       // instruction u = wave + 8*i: stage rows 16u .. 16u+15; i < 2: X pixels, else W channels
@@ -422,7 +406,7 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
     }
   };
 
-  const unsigned lds0 = ks_lds_addr(smem_raw);
+  const unsigned lds0 = lds_addr(smem_raw);
   unsigned offA[2], offB[PB];
   int fA[2], fB[PB];
 #pragma unroll
@@ -448,15 +432,15 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
   u32x4 fa[2][2], fb[2][PB];                       // [buffer][block]: the fragments of k-step u live in buffer u & 1
   auto read_frags = [&](int buf, unsigned sbo, int ks) {
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) ks_read16(fa[buf][cb], offA[cb] + sbo + (((2 * ks + h) ^ fA[cb]) << 4));
+    for (int cb = 0; cb < 2; ++cb) lds_read16(fa[buf][cb], offA[cb] + sbo + (((2 * ks + h) ^ fA[cb]) << 4));
 #pragma unroll
-    for (int p = 0; p < PB; ++p) ks_read16(fb[buf][p], offB[p] + sbo + (((2 * ks + h) ^ fB[p]) << 4));
+    for (int p = 0; p < PB; ++p) lds_read16(fb[buf][p], offB[p] + sbo + (((2 * ks + h) ^ fB[p]) << 4));
   };
   auto fence_frags = [&](int buf) {
-    ks_fence<0>(fa[buf][0], true);
-    ks_fence<0>(fa[buf][1], false);
+    lds_fence<0>(fa[buf][0], true);
+    lds_fence<0>(fa[buf][1], false);
 #pragma unroll
-    for (int p = 0; p < PB; ++p) ks_fence<0>(fb[buf][p], false);
+    for (int p = 0; p < PB; ++p) lds_fence<0>(fb[buf][p], false);
   };
   auto mfmas = [&](int buf) {
 #pragma unroll
@@ -524,8 +508,8 @@ __device__ __forceinline__ void conv1x1_kstream256_body(const T* __restrict__ X,
           q[4 * g + 2 + t] = sw[1];
         }
       const int ch0 = wn * 8 + cb * 4 + h;
-      ks_write16(orow + (((ch0) ^ ks_oswz(trow)) << 4), (u32x4){q[0], q[1], q[2], q[3]});
-      ks_write16(orow + (((ch0 + 2) ^ ks_oswz(trow)) << 4), (u32x4){q[4], q[5], q[6], q[7]});
+      lds_write16(orow + (((ch0) ^ out_swz(trow)) << 4), (u32x4){q[0], q[1], q[2], q[3]});
+      lds_write16(orow + (((ch0 + 2) ^ out_swz(trow)) << 4), (u32x4){q[4], q[5], q[6], q[7]});
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -603,89 +587,37 @@ KsPlan ks_plan(int M, int K, int N) {
   return p;
 }
 
-template <int WN, int PB, bool MOM, bool ADD>
-int ks_launch_m(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
-                hipStream_t st, const void* a, const AddendGeo& ag) {
-  typedef KsGeo<WN, PB> G;
-  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_f16_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream_f16_kernel<WN, PB, MOM, ADD>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
-                       (f16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const f16_t*)a, ag);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_kernel<WN, PB, MOM, ADD>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream_kernel<WN, PB, MOM, ADD>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const bf16_t*)a, ag);
-  }
-  return hip_status(hipGetLastError());
+dim3 ks_grid(const KsPlan& p) { return dim3((p.tiles_m * p.groups_n + 7) / 8 * 8); }
+
+// f(WN, PB), as integral constants, for the tile of the three-stage kernel the plan picked
+template <typename F>
+int ks_instance(const KsPlan& p, F&& f) {
+  if (p.wn == 4) return p.pb == 2 ? f(Int<4>(), Int<2>()) : f(Int<4>(), Int<1>());
+  return p.pb == 2 ? f(Int<2>(), Int<2>()) : f(Int<2>(), Int<1>());
 }
-// a != null: the addend form (never with records)
-template <int WN, int PB>
+
+// the plain form (MOM: with the records `part`) or the addend form (ADD, never with records) of the kernel the plan picked
+template <bool MOM, bool ADD>
 int ks_launch(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
               hipStream_t st, const void* a, const AddendGeo& ag) {
-  if (a) return ks_launch_m<WN, PB, false, true>(p, x, w, y, nullptr, M, K, N, dtype, st, a, ag);
-  return part ? ks_launch_m<WN, PB, true, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag)
-              : ks_launch_m<WN, PB, false, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
-}
-template <bool MOM, bool ADD>
-int ks_launch256(const KsPlan& p, const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype,
-                 hipStream_t st, const void* a, const AddendGeo& ag) {
-  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_f16_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream256_f16_kernel<MOM, ADD>), grid, block, Ks256::kLds, st, (const f16_t*)x, (const f16_t*)w,
-                       (f16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const f16_t*)a, ag);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_kernel<MOM, ADD>), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream256_kernel<MOM, ADD>), grid, block, Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       (bf16_t*)y, part, M, N, K, p.tiles_m, p.groups_n, (const bf16_t*)a, ag);
-  }
-  return hip_status(hipGetLastError());
+  const dim3 grid = ks_grid(p), block(kKsWaves * kWave);
+  if (p.big)
+    return launch_by_dtype(dtype, conv1x1_kstream256_kernel<MOM, ADD>, conv1x1_kstream256_f16_kernel<MOM, ADD>, grid, block,
+                           Ks256::kLds, st, x, w, y, part, M, N, K, p.tiles_m, p.groups_n, a, ag);
+  return ks_instance(p, [&](auto wn, auto pb) {
+    constexpr int WN = decltype(wn)::value, PB = decltype(pb)::value;
+    return launch_by_dtype(dtype, conv1x1_kstream_kernel<WN, PB, MOM, ADD>, conv1x1_kstream_f16_kernel<WN, PB, MOM, ADD>, grid,
+                           block, KsGeo<WN, PB>::kLds, st, x, w, y, part, M, N, K, p.tiles_m, p.groups_n, a, ag);
+  });
 }
 
 int ks_dispatch(const void* x, const void* w, void* y, float* part, int M, int K, int N, int dtype, hipStream_t st,
                 const void* a, const AddendGeo& ag) {
   const KsPlan p = ks_plan(M, K, N);
   if (!p.wn || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
-  if (p.big) {
-    if (a) return ks_launch256<false, true>(p, x, w, y, nullptr, M, K, N, dtype, st, a, ag);
-    return part ? ks_launch256<true, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag)
-                : ks_launch256<false, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
-  }
-  if (p.wn == 4) return p.pb == 2 ? ks_launch<4, 2>(p, x, w, y, part, M, K, N, dtype, st, a, ag) : ks_launch<4, 1>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
-  return p.pb == 2 ? ks_launch<2, 2>(p, x, w, y, part, M, K, N, dtype, st, a, ag) : ks_launch<2, 1>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
-}
-
-template <int WN, int PB>
-int ks_launch_affine(const KsPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M,
-                     int K, int N, int dtype, hipStream_t st) {
-  typedef KsGeo<WN, PB> G;
-  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_f16_affine_kernel<WN, PB>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream_f16_affine_kernel<WN, PB>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
-                       sc, sh, relu, (f16_t*)y, M, N, K, p.tiles_m, p.groups_n);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream_affine_kernel<WN, PB>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_kstream_affine_kernel<WN, PB>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       sc, sh, relu, (bf16_t*)y, M, N, K, p.tiles_m, p.groups_n);
-  }
-  return hip_status(hipGetLastError());
-}
-
-int ks_launch256_affine(const KsPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y,
-                        int M, int K, int N, int dtype, hipStream_t st) {
-  const dim3 grid((p.tiles_m * p.groups_n + 7) / 8 * 8), block(kKsWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_f16_affine_kernel), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL(conv1x1_kstream256_f16_affine_kernel, grid, block, Ks256::kLds, st, (const f16_t*)x, (const f16_t*)w,
-                       sc, sh, relu, (f16_t*)y, M, N, K, p.tiles_m, p.groups_n);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_kstream256_affine_kernel), Ks256::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL(conv1x1_kstream256_affine_kernel, grid, block, Ks256::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       sc, sh, relu, (bf16_t*)y, M, N, K, p.tiles_m, p.groups_n);
-  }
-  return hip_status(hipGetLastError());
+  if (a) return ks_launch<false, true>(p, x, w, y, nullptr, M, K, N, dtype, st, a, ag);
+  return part ? ks_launch<true, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag)
+              : ks_launch<false, false>(p, x, w, y, part, M, K, N, dtype, st, a, ag);
 }
 
 }  // namespace
@@ -710,11 +642,15 @@ int launch_conv1x1_kstream_affine(const void* x, const void* w, const float* sc,
                                   int N, int dtype, hipStream_t st) {
   const KsPlan p = ks_plan(M, K, N);
   if (!p.wn || (dtype != MRLA_BF16 && dtype != MRLA_F16)) return MRLA_EUNSUPPORTED;
-  if (p.big) return ks_launch256_affine(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
-  if (p.wn == 4) return p.pb == 2 ? ks_launch_affine<4, 2>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st)
-                                  : ks_launch_affine<4, 1>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
-  return p.pb == 2 ? ks_launch_affine<2, 2>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st)
-                   : ks_launch_affine<2, 1>(p, x, w, sc, sh, relu, y, M, K, N, dtype, st);
+  const dim3 grid = ks_grid(p), block(kKsWaves * kWave);
+  if (p.big)
+    return launch_by_dtype(dtype, conv1x1_kstream256_affine_kernel, conv1x1_kstream256_f16_affine_kernel, grid, block,
+                           Ks256::kLds, st, x, w, sc, sh, relu, y, M, N, K, p.tiles_m, p.groups_n);
+  return ks_instance(p, [&](auto wn, auto pb) {
+    constexpr int WN = decltype(wn)::value, PB = decltype(pb)::value;
+    return launch_by_dtype(dtype, conv1x1_kstream_affine_kernel<WN, PB>, conv1x1_kstream_f16_affine_kernel<WN, PB>, grid, block,
+                           KsGeo<WN, PB>::kLds, st, x, w, sc, sh, relu, y, M, N, K, p.tiles_m, p.groups_n);
+  });
 }
 
 }  // namespace mrla

@@ -47,6 +47,7 @@
 #include <type_traits>
 
 #include "conv1x1_elem.h"
+#include "conv1x1_lds.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -60,7 +61,6 @@ typedef __attribute__((address_space(3))) wg_s16x4* lds_s16x4_ptr;
 constexpr int kPC = 32;                 // pixels per stage
 constexpr int kWgStages = 4;            // LDS stages: one being read, one being refilled, two in flight
 constexpr int kWgWaves = 4;
-#define MRLA_WG_FLAGS 0x00020000        /* raw buffer descriptor word 3 (as nhwc_rows.h) */
 constexpr int kWgTarget = 256;          // workgroups: one per CU (the stages, not a second workgroup, hide the DMA latency;
                                         // every workgroup costs a partial tile of up to 128 KB written and re-read)
 
@@ -115,9 +115,6 @@ template <typename T>
 __device__ __forceinline__ typename Elem16<T>::x8 frag_value(const Frag& f) {
   return __builtin_bit_cast(typename Elem16<T>::x8, __builtin_shufflevector(f.lo, f.hi, 0, 1, 2, 3, 4, 5, 6, 7));
 }
-__device__ __forceinline__ unsigned wg_lds_addr(const void* p) {
-  return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
-}
 
 // what the BN form reads and writes beside (g = dY's slot, X, part)
 struct WgBnArgs {
@@ -134,19 +131,14 @@ struct WgDxArgs {
 };
 constexpr int kDxRowB = 64 * 2 + 16;      // padded row of the dX staging tile (64 channels of one pixel), as conv1x1.hip's
 
+// The 16-byte write and the fence of the rewrite and of the dX form are conv1x1_lds.h's.  The read stays written out here:
+// its output is early-clobber, and with lds_read16's plain output the two dX kernels compile to another instruction stream.
 __device__ __forceinline__ void wg_read16(u32x4& v, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1" : "=&v"(v) : "v"(addr));
 }
 template <int OFF>
 __device__ __forceinline__ void wg_read16_at(u32x4& v, unsigned addr) {
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=&v"(v) : "v"(addr), "n"(OFF));
-}
-__device__ __forceinline__ void wg_write16(unsigned addr, const u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-__device__ __forceinline__ void wg_fence16(u32x4& v, bool wait) {
-  if (wait) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v) : : "memory");
-  else asm volatile("" : "+v"(v) : : "memory");                 // rides on the wait of the piece fenced just before
 }
 
 // grid: tiles * splits workgroups (tiles = (N/TN)*(K/TK)) padded to a multiple of 8; 256 threads; LDS = ST * SB
@@ -180,8 +172,8 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   const int nch = min(chunks_per_wg, chunks_total - c_begin);      // >= 1 by construction of the grid
 
   // ---- DMA plan: wave-instruction u of a stage moves 1 KB = 64/CPR tile rows; this wave issues u = wave + 4*i ----
-  const auto rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(dY), 0, (int)((size_t)M * N * 2), MRLA_WG_FLAGS);
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_WG_FLAGS);
+  const auto rsY = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(dY), 0, (int)((size_t)M * N * 2), kBufFlags);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), kBufFlags);
   unsigned voffY[G::NIY], voffX[G::NIX];
 #pragma unroll
   for (int i = 0; i < G::NIY; ++i) {
@@ -196,7 +188,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   const unsigned advY = (unsigned)PC * N * 2, advX = (unsigned)PC * K * 2;
   // BN: xb has dY's shape, so its pieces are fetched at dY's offsets (and are killed with them)
   const auto rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(BN ? bn.xb : nullptr), 0,
-                                                     BN ? (int)((size_t)M * N * 2) : 0, MRLA_WG_FLAGS);
+                                                     BN ? (int)((size_t)M * N * 2) : 0, kBufFlags);
   int issued = 0;
   auto issue = [&](int stage) {
     unsigned char* sb = smem_raw + stage * SB;
@@ -217,7 +209,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 
   // ---- this wave's operand addresses (stage- and k-step-relative) ----
   const int wn = wave / G::WK, wk = wave - wn * G::WK;
-  const unsigned lds0 = wg_lds_addr(smem_raw);
+  const unsigned lds0 = lds_addr(smem_raw);
   unsigned offA[G::BN], offB[G::BK];
 #pragma unroll
   for (int i = 0; i < G::BN; ++i) offA[i] = lds0 + tr_offset<CPRY>(lane, 0, wn * G::WTN + i * 32);
@@ -236,7 +228,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   float cbv[BN ? 24 : 1], scv[BN ? 8 : 1], shv[BN ? 8 : 1];
   unsigned tbase[BN ? G::NIY : 1], toff = 0;             // byte offsets of the pieces of chunk 0; chunks rewritten * advY
   const auto rsO = __builtin_amdgcn_make_buffer_rsrc(BN ? bn.dy_out : nullptr, 0, BN ? (int)((size_t)M * N * 2) : 0,
-                                                     MRLA_WG_FLAGS);
+                                                     kBufFlags);
   const unsigned tlimit = (unsigned)((size_t)M * N * 2);
   const unsigned skill = tk == 0 ? 0u : 0x80000000u;     // every k-tile rewrites its own copy; k-tile 0 stores dy_out
   if constexpr (BN) {
@@ -269,7 +261,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   // ---- DX: this wave's 32 rows of W^T as MFMA A fragments (all 16 k-steps: 64 registers), the store lane's first offset ----
   // Waves 0/1 take the two 32-channel output blocks of the even chunks, waves 2/3 those of the odd ones.
   u32x4 wa[DX ? 16 : 1];
-  const auto rsD = __builtin_amdgcn_make_buffer_rsrc(DX ? dxa.dx : nullptr, 0, DX ? (int)((size_t)M * K * 2) : 0, MRLA_WG_FLAGS);
+  const auto rsD = __builtin_amdgcn_make_buffer_rsrc(DX ? dxa.dx : nullptr, 0, DX ? (int)((size_t)M * K * 2) : 0, kBufFlags);
   const unsigned dlimit = (unsigned)((size_t)M * K * 2);
   const int dr = lane & 31, dh = lane >> 5, dblk = wave & 1;
   unsigned doff = 0;                                     // this lane's 16 bytes of the dX lines of the chunk stored next
@@ -294,8 +286,8 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
     }
 #pragma unroll
     for (int i = 0; i < G::NIY; ++i) {
-      wg_fence16(gq[i], i == 0);
-      wg_fence16(xq[i], false);
+      lds_fence<0>(gq[i], i == 0);
+      lds_fence<0>(xq[i], false);
     }
 #pragma unroll
     for (int i = 0; i < G::NIY; ++i) {
@@ -317,7 +309,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
         }
         o[w] = live ? Elem16<T>::pack(y[0], y[1]) : 0u;
       }
-      wg_write16(at + i * (kWgWaves * 1024), o);
+      lds_write16(at + i * (kWgWaves * 1024), o);
       if constexpr (!DX) __builtin_amdgcn_raw_buffer_store_b128(o, rsO, (live ? off : 0x80000000u) | skill, 0, 0);
     }
     toff += advY;
@@ -335,7 +327,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) wg_read16(bq[ks], rowa + (((2 * ks + dh) ^ sw) << 4));
 #pragma unroll
-    for (int ks = 0; ks < 16; ++ks) wg_fence16(bq[ks], ks == 0);
+    for (int ks = 0; ks < 16; ++ks) lds_fence<0>(bq[ks], ks == 0);
     wg_f32x16 d;
 #pragma unroll
     for (int e = 0; e < 16; ++e) d[e] = 0.f;
@@ -357,8 +349,8 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
       }
     }
     const unsigned to = lds0 + sbo + G::SB + dr * kDxRowB + (dblk * 32 + dh * 8) * 2;
-    wg_write16(to, (u32x4){p[0], p[1], p[2], p[3]});
-    wg_write16(to + 32, (u32x4){p[4], p[5], p[6], p[7]});
+    lds_write16(to, (u32x4){p[0], p[1], p[2], p[3]});
+    lds_write16(to + 32, (u32x4){p[4], p[5], p[6], p[7]});
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   };
   // DX: the 32 lines (128 bytes) of the chunk staged at sbo, one 16-byte piece per lane of the workgroup; behind the
@@ -367,7 +359,7 @@ __device__ __forceinline__ void conv1x1_wgrad_body(const T* __restrict__ dY, con
   auto dx_store = [&](unsigned sbo) {
     u32x4 v;
     wg_read16(v, lds0 + sbo + G::SB + (wave * 8 + (lane >> 3)) * kDxRowB + (lane & 7) * 16);
-    wg_fence16(v, true);
+    lds_fence<0>(v, true);
     __builtin_amdgcn_raw_buffer_store_b128(v, rsD, doff < dlimit ? doff : 0x80000000u, 0, 0);
     doff += advX;
   };
@@ -583,55 +575,30 @@ WgPlan wgrad_plan(int M, int K, int N) {
   return p;
 }
 
+dim3 wg_grid(const WgPlan& p) { return dim3((p.tiles * p.splits + 7) / 8 * 8); }
+
+// bn [opt]: the BN form -- dy is then g, and a stage carries the xb tile as well
 template <int TN, int TK, int ST, int PC>
 int launch_tile(const WgPlan& p, const void* dy, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st,
                 const WgBnArgs* bn = nullptr) {
   typedef WgGeo<TN, TK, PC> G;
-  const dim3 grid((p.tiles * p.splits + 7) / 8 * 8), block(kWgWaves * kWave);
-  if (bn) {                        // dy is g; a stage carries the xb tile as well
-    const size_t lds = (size_t)ST * (G::SB + G::YB);
-    static_assert((size_t)ST * (G::SB + G::YB) <= 160 * 1024, "LDS of a CU");
-    if (dtype == MRLA_F16) {
-      if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_f16_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
-      hipLaunchKernelGGL((conv1x1_wgrad_bn_f16_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const f16_t*)dy, (const f16_t*)x,
-                         part, M, N, K, p.chunks_per_wg, p.splits, *bn);
-    } else {
-      if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
-      hipLaunchKernelGGL((conv1x1_wgrad_bn_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const bf16_t*)dy, (const bf16_t*)x,
-                         part, M, N, K, p.chunks_per_wg, p.splits, *bn);
-    }
-    return MRLA_OK;
-  }
-  const size_t lds = (size_t)ST * G::SB;
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const f16_t*)dy, (const f16_t*)x, part,
-                       M, N, K, p.chunks_per_wg, p.splits);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_kernel<TN, TK, ST, PC>), lds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wgrad_kernel<TN, TK, ST, PC>), grid, block, lds, st, (const bf16_t*)dy, (const bf16_t*)x, part,
-                       M, N, K, p.chunks_per_wg, p.splits);
-  }
-  return MRLA_OK;
+  static_assert((size_t)ST * (G::SB + G::YB) <= 160 * 1024, "LDS of a CU");
+  const dim3 block(kWgWaves * kWave);
+  if (bn)
+    return launch_by_dtype(dtype, conv1x1_wgrad_bn_kernel<TN, TK, ST, PC>, conv1x1_wgrad_bn_f16_kernel<TN, TK, ST, PC>, wg_grid(p),
+                           block, (size_t)ST * (G::SB + G::YB), st, dy, x, part, M, N, K, p.chunks_per_wg, p.splits, *bn);
+  return launch_by_dtype(dtype, conv1x1_wgrad_kernel<TN, TK, ST, PC>, conv1x1_wgrad_f16_kernel<TN, TK, ST, PC>, wg_grid(p), block,
+                         (size_t)ST * G::SB, st, dy, x, part, M, N, K, p.chunks_per_wg, p.splits);
 }
 
 // the BN + dX form: the BN form's grid and LDS (the dX staging lives in the xb tiles)
 int launch_tile_dx(const WgPlan& p, const void* g, const void* x, float* part, int M, int K, int N, int dtype, hipStream_t st,
                    const WgBnArgs& bn, const WgDxArgs& dxa) {
   typedef WgGeo<256, 64, kPC> G;
-  const dim3 grid((p.tiles * p.splits + 7) / 8 * 8), block(kWgWaves * kWave);
   constexpr size_t lds = (size_t)kWgStages * (G::SB + G::YB);
   static_assert(lds <= 160 * 1024 && kPC * kDxRowB <= G::YB, "LDS of a CU / the staging tile inside the xb tile");
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_dx_f16_kernel<kWgStages>), lds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wgrad_bn_dx_f16_kernel<kWgStages>), grid, block, lds, st, (const f16_t*)g, (const f16_t*)x, part, M,
-                       N, K, p.chunks_per_wg, p.splits, bn, dxa);
-  } else {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wgrad_bn_dx_kernel<kWgStages>), lds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wgrad_bn_dx_kernel<kWgStages>), grid, block, lds, st, (const bf16_t*)g, (const bf16_t*)x, part, M,
-                       N, K, p.chunks_per_wg, p.splits, bn, dxa);
-  }
-  return MRLA_OK;
+  return launch_by_dtype(dtype, conv1x1_wgrad_bn_dx_kernel<kWgStages>, conv1x1_wgrad_bn_dx_f16_kernel<kWgStages>, wg_grid(p),
+                         dim3(kWgWaves * kWave), lds, st, g, x, part, M, N, K, p.chunks_per_wg, p.splits, bn, dxa);
 }
 
 }  // namespace
@@ -685,20 +652,17 @@ static int launch_wgrad(const void* dy, const void* x, float* part, void* dw, in
     MRLA_WG_TILE(128, 256) MRLA_WG_TILE(256, 64) MRLA_WG_TILE(256, 128)
 #undef MRLA_WG_TILE
   }
-  if (rc != MRLA_OK) return rc;
+  if (rc != MRLA_OK) return rc;      // (also a failed launch of the tile kernel: the sum is not enqueued behind it)
   const int NK = N * K;
+  const dim3 grid(NK / 64), block(256);
   if (dw_f32)      // the fp32 master weight's gradient directly (no cast kernel behind an autocast convolution)
-    hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<float>, dim3(NK / 64), dim3(256), 0, st, part, (float*)dw, p.splits, NK);
-  else if (dtype == MRLA_F16)
-    hipLaunchKernelGGL(conv1x1_wgrad_reduce_f16_kernel, dim3(NK / 64), dim3(256), 0, st, part, (f16_t*)dw, p.splits, NK);
-  else
-    hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<bf16_t>, dim3(NK / 64), dim3(256), 0, st, part, (bf16_t*)dw, p.splits, NK);
-  return hip_status(hipGetLastError());
+    return launch_kernel(conv1x1_wgrad_reduce_kernel<float>, grid, block, 0, st, part, dw, p.splits, NK);
+  return launch_by_dtype(dtype, conv1x1_wgrad_reduce_kernel<bf16_t>, conv1x1_wgrad_reduce_f16_kernel, grid, block, 0, st, part,
+                         dw, p.splits, NK);
 }
 
 int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, int NK, hipStream_t st) {
-  hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel<float>, dim3(NK / 64), dim3(256), 0, st, part, dw, splits, NK);
-  return hip_status(hipGetLastError());
+  return launch_kernel(conv1x1_wgrad_reduce_kernel<float>, dim3(NK / 64), dim3(256), 0, st, part, dw, splits, NK);
 }
 
 int launch_conv1x1_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int M, int K, int N, int dtype,

@@ -25,12 +25,13 @@
 //     the exchange.  There a register's channel depends on the lane half only and the wave's 32 channels are wave-uniform,
 //     so the 32 + 32 fp32 coefficients are scalar loads into SGPRs, selected per half -- the row-store lanes would need 16
 //     VGPRs for theirs, kept across the MFMAs of every block, which the K = 64 and K = 128 instances do not have to spare;
-//   * one barrier per pixel block; LDS traffic of the pipeline is inline asm with explicit waits (the compiler would put
-//     `s_waitcnt vmcnt(0)` in front of every LDS access it sees after an LDS-DMA load).
+//   * one barrier per pixel block; LDS traffic of the pipeline is inline asm with explicit waits (conv1x1_lds.h: the
+//     compiler would put `s_waitcnt vmcnt(0)` in front of every LDS access it sees after an LDS-DMA load).
 #include <algorithm>
 
 #include "conv1x1_addend.h"
 #include "conv1x1_affine.h"
+#include "conv1x1_lds.h"
 #include "mrla_device.h"
 #include "mrla_kernels.h"
 
@@ -39,7 +40,6 @@ namespace {
 
 typedef c1_f32x16 cw_f32x16;
 
-#define MRLA_CW_FLAGS 0x00020000          /* raw buffer descriptor word 3 (as nhwc_rows.h) */
 constexpr int kCwWaves = 8;
 constexpr int kCwTN = 256;                // output channels per workgroup
 constexpr int kOutB = 32 * kCwTN * 2;     // bytes of an output / addend tile [32 px][256 ch]
@@ -59,25 +59,9 @@ struct CwGeo {
   static constexpr int kLds = kDummy + 1024;
 };
 
-__device__ __forceinline__ unsigned cw_lds_addr(const void* p) {
-  return (unsigned)(size_t)((__attribute__((address_space(3))) const char*)p);
-}
-__device__ __forceinline__ void cw_read16(u32x4& v, unsigned addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr));
-}
-__device__ __forceinline__ void cw_write16(unsigned addr, const u32x4& v) {
-  asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void cw_fence(u32x4& v, bool wait) {
-  if (wait) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-  else asm volatile("" : "+v"(v)::"memory");
-}
-
-// chunk swizzle of X rows (CPR 16-byte chunks per row) and of output-tile rows (32 chunks)
+// chunk swizzle of X rows (CPR 16-byte chunks per row); the output-tile rows (32 chunks) have out_swz
 template <int CPR>
 __device__ __forceinline__ int cw_swz(int row) { return CPR >= 16 ? (row & 15) : ((row >> 1) & 7); }
-__device__ __forceinline__ int cw_oswz(int row) { return row & 7; }
 
 template <typename T, int KS, bool MOM, bool ADD, bool SP, bool AFF = false>
 __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const T* __restrict__ W, const T* __restrict__ A,
@@ -128,9 +112,9 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
   }
 
   // ---- DMA plan ----
-  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), MRLA_CW_FLAGS);
+  const auto rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(X), 0, (int)((size_t)M * K * 2), kBufFlags);
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(ADD ? A : X), 0,
-                                                     ADD ? (int)((size_t)(SP ? ag.rows : M) * N * 2) : 0, MRLA_CW_FLAGS);
+                                                     ADD ? (int)((size_t)(SP ? ag.rows : M) * N * 2) : 0, kBufFlags);
   unsigned voffX[G::NIX], voffA[ADD ? G::NIA : 1];
   constexpr bool kIdleWaves = G::XB / 1024 < kCwWaves;          // K = 64: four real X instructions, waves 4-7 issue a dummy
   const bool idle = kIdleWaves && wave >= G::XB / 1024;
@@ -145,7 +129,7 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
     for (int i = 0; i < G::NIA; ++i) {
       const int u = wave + kCwWaves * i, row = u * 2 + lane / 32, cp = lane % 32;
       // SP: the position inside the pixel's row only; the row is found per unit
-      voffA[i] = (unsigned)((SP ? (size_t)0 : ((size_t)u_begin * 32 + row) * N * 2) + cg * (kCwTN * 2) + ((cp ^ cw_oswz(row)) << 4));
+      voffA[i] = (unsigned)((SP ? (size_t)0 : ((size_t)u_begin * 32 + row) * N * 2) + cg * (kCwTN * 2) + ((cp ^ out_swz(row)) << 4));
     }
   }
   const unsigned advX = 32u * K * 2, advA = 32u * (unsigned)N * 2;
@@ -179,16 +163,16 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
   };
 
   // ---- addresses ----
-  const unsigned lds0 = cw_lds_addr(smem_raw);
+  const unsigned lds0 = lds_addr(smem_raw);
   const int fx = cw_swz<CPR>(r);
   const unsigned xrow = lds0 + r * (K * 2);                                  // + slot*XB + (((2ks+h) ^ fx) << 4)
   // this lane's two 16-byte pieces of its pixel's output row: channels wave*32 + h*8 .. and wave*32 + 16 + h*8 ..
   const int oc0 = wave * 4 + h, oc1 = oc0 + 2;
   const unsigned orow = lds0 + G::kXRing + r * (kCwTN * 2);
-  const unsigned opc0 = orow + ((oc0 ^ cw_oswz(r)) << 4), opc1 = orow + ((oc1 ^ cw_oswz(r)) << 4);
+  const unsigned opc0 = orow + ((oc0 ^ out_swz(r)) << 4), opc1 = orow + ((oc1 ^ out_swz(r)) << 4);
   // cooperative store: thread -> (row, chunk) of the tile, two rows 16 apart
   const int srow = threadIdx.x >> 5, schunk = threadIdx.x & 31;
-  const unsigned sld0 = lds0 + G::kXRing + srow * (kCwTN * 2) + ((schunk ^ cw_oswz(srow)) << 4);
+  const unsigned sld0 = lds0 + G::kXRing + srow * (kCwTN * 2) + ((schunk ^ out_swz(srow)) << 4);
   const unsigned sld1 = sld0 + 16 * (kCwTN * 2);                             // (row + 16: same swizzle, (row+16)&7 == row&7)
   T* yrow = Y + ((size_t)u_begin * 32 + srow) * N + cg * kCwTN + schunk * 8;
 
@@ -222,18 +206,18 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     u32x4 xf[2][KC];
 #pragma unroll
-    for (int ks = 0; ks < KC; ++ks) cw_read16(xf[0][ks], xs + (((2 * ks + h) ^ fx) << 4));
+    for (int ks = 0; ks < KC; ++ks) lds_read16(xf[0][ks], xs + (((2 * ks + h) ^ fx) << 4));
 #pragma unroll
     for (int kc = 0; kc < NCH; ++kc) {
       const int cur = kc & 1;
       if (kc + 1 < NCH) {
 #pragma unroll
-        for (int ks = 0; ks < KC; ++ks) cw_read16(xf[cur ^ 1][ks], xs + (((2 * ((kc + 1) * KC + ks) + h) ^ fx) << 4));
+        for (int ks = 0; ks < KC; ++ks) lds_read16(xf[cur ^ 1][ks], xs + (((2 * ((kc + 1) * KC + ks) + h) ^ fx) << 4));
 #pragma unroll
-        for (int ks = 0; ks < KC; ++ks) cw_fence<KC>(xf[cur][ks], ks == 0);
+        for (int ks = 0; ks < KC; ++ks) lds_fence<KC>(xf[cur][ks], ks == 0);
       } else {
 #pragma unroll
-        for (int ks = 0; ks < KC; ++ks) cw_fence<0>(xf[cur][ks], ks == 0);
+        for (int ks = 0; ks < KC; ++ks) lds_fence<0>(xf[cur][ks], ks == 0);
       }
 #pragma unroll
       for (int ks = 0; ks < KC; ++ks)
@@ -257,10 +241,10 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
           av[8 * g + 4 + q] = __uint_as_float(sw[1]);
         }
       u32x4 a0, a1;
-      cw_read16(a0, opc0 + os);
-      cw_read16(a1, opc1 + os);
-      cw_fence<0>(a0, true);
-      cw_fence<0>(a1, false);
+      lds_read16(a0, opc0 + os);
+      lds_read16(a1, opc1 + os);
+      lds_fence<0>(a0, true);
+      lds_fence<0>(a1, false);
       const unsigned aw[8] = {a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
@@ -332,8 +316,8 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
           p[4 * g + 2 + q] = sw[1];
         }
     }
-    cw_write16(opc0 + os, (u32x4){p[0], p[1], p[2], p[3]});
-    cw_write16(opc1 + os, (u32x4){p[4], p[5], p[6], p[7]});
+    lds_write16(opc0 + os, (u32x4){p[0], p[1], p[2], p[3]});
+    lds_write16(opc1 + os, (u32x4){p[4], p[5], p[6], p[7]});
     // hand-over: my part of unit u+1 has landed, my tile pieces are written; after the barrier everybody's are, and
     // unit u's X block is free for the DMA of unit u+UST-1
     if (u < UST) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(C_EARLY) : "memory");
@@ -346,10 +330,10 @@ __device__ __forceinline__ void conv1x1_wide_body(const T* __restrict__ X, const
     // whole 512-byte rows out: 32 lanes per pixel row, rows srow and srow + 16
     {
       u32x4 v0, v1;
-      cw_read16(v0, sld0 + os);
-      cw_read16(v1, sld1 + os);
-      cw_fence<0>(v0, true);
-      cw_fence<0>(v1, false);
+      lds_read16(v0, sld0 + os);
+      lds_read16(v1, sld1 + os);
+      lds_fence<0>(v0, true);
+      lds_fence<0>(v1, false);
       const int pix = (u_begin + u) * 32 + srow;
       T* yp = yrow + (size_t)u * 32 * N;
       if (pix < M) *reinterpret_cast<u32x4*>(yp) = v0;
@@ -443,51 +427,32 @@ CwPlan cw_plan(int M, int K, int N) {
   const int want = std::max(1, std::min(nblk, (256 + groups - 1) / groups));          // one workgroup per CU
   const int upw = (nblk + want - 1) / want;
   const int splits = (nblk + upw - 1) / upw;
-  // the statistics kernel takes (rows, M / rows): pad the partial buffer with zero rows up to the next divisor of M
-  int rows = splits;
-  while (rows <= 2 * splits + 64 && M % rows) ++rows;
-  if (M % rows) return p;
+  const int rows = pad_rows_to_divisor(M, splits);
+  if (!rows) return p;
   p.groups = groups; p.splits = splits; p.units_per_wg = upw; p.rows = rows;
   return p;
 }
+
+// f(KS) with KS = K / 16 as an integral constant, for the K this file takes
+template <typename F>
+int cw_instance(int K, F&& f) {
+  switch (K) {
+    case 64: return f(Int<4>());
+    case 128: return f(Int<8>());
+    case 256: return f(Int<16>());
+    default: return MRLA_EUNSUPPORTED;
+  }
+}
+
+dim3 cw_grid(const CwPlan& p) { return dim3((p.groups * p.splits + 7) / 8 * 8); }
 
 template <int KS, bool MOM, bool ADD, bool SP = false>
 int cw_launch(const CwPlan& p, const void* x, const void* w, const void* a, void* y, float* part, int M, int N, int dtype,
               hipStream_t st, const AddendGeo& ag = AddendGeo()) {
   typedef CwGeo<KS, ADD> G;
   static_assert(G::kLds <= 160 * 1024, "LDS");
-  const dim3 grid((p.groups * p.splits + 7) / 8 * 8), block(kCwWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_f16_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wide_f16_kernel<KS, MOM, ADD, SP>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w,
-                       (const f16_t*)a, (f16_t*)y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
-  } else if (dtype == MRLA_BF16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_kernel<KS, MOM, ADD, SP>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wide_kernel<KS, MOM, ADD, SP>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w,
-                       (const bf16_t*)a, (bf16_t*)y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
-  } else {
-    return MRLA_EUNSUPPORTED;
-  }
-  return hip_status(hipGetLastError());
-}
-
-template <int KS>
-int cw_launch_affine(const CwPlan& p, const void* x, const void* w, const float* sc, const float* sh, int relu, void* y, int M,
-                     int N, int dtype, hipStream_t st) {
-  typedef CwGeo<KS, false> G;
-  const dim3 grid((p.groups * p.splits + 7) / 8 * 8), block(kCwWaves * kWave);
-  if (dtype == MRLA_F16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_f16_affine_kernel<KS>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wide_f16_affine_kernel<KS>), grid, block, G::kLds, st, (const f16_t*)x, (const f16_t*)w, sc, sh,
-                       relu, (f16_t*)y, M, N, p.units_per_wg, p.splits);
-  } else if (dtype == MRLA_BF16) {
-    if (lds_opt_in(reinterpret_cast<const void*>(conv1x1_wide_affine_kernel<KS>), G::kLds) != hipSuccess) return MRLA_EHIP;
-    hipLaunchKernelGGL((conv1x1_wide_affine_kernel<KS>), grid, block, G::kLds, st, (const bf16_t*)x, (const bf16_t*)w, sc, sh,
-                       relu, (bf16_t*)y, M, N, p.units_per_wg, p.splits);
-  } else {
-    return MRLA_EUNSUPPORTED;
-  }
-  return hip_status(hipGetLastError());
+  return launch_by_dtype(dtype, conv1x1_wide_kernel<KS, MOM, ADD, SP>, conv1x1_wide_f16_kernel<KS, MOM, ADD, SP>, cw_grid(p),
+                         dim3(kCwWaves * kWave), G::kLds, st, x, w, a, y, part, M, N, p.units_per_wg, p.splits, p.rows, ag);
 }
 
 }  // namespace
@@ -501,33 +466,27 @@ int conv1x1_wide_rows(int M, int K, int N) {
 int conv1x1_wide_plan(int M, int K, int N, int add, int* out) {
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
-  const int ks = K / 16;
   out[0] = p.units_per_wg;
-  out[1] = add ? (ks == 16 ? CwGeo<16, true>::UST : ks == 8 ? CwGeo<8, true>::UST : CwGeo<4, true>::UST)
-               : (ks == 16 ? CwGeo<16, false>::UST : ks == 8 ? CwGeo<8, false>::UST : CwGeo<4, false>::UST);
   out[2] = p.groups * p.splits;
   out[3] = p.rows;
-  return MRLA_OK;
+  return cw_instance(K, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    out[1] = add ? CwGeo<KS, true>::UST : CwGeo<KS, false>::UST;
+    return (int)MRLA_OK;
+  });
 }
 
 int launch_conv1x1_wide(const void* x, const void* w, const void* addend, void* y, float* part, int M, int K, int N,
                         int dtype, hipStream_t st) {
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
-#define MRLA_CW_CALL(KS)                                                                         \
-  {                                                                                              \
-    if (addend) return part ? cw_launch<KS, true, true>(p, x, w, addend, y, part, M, N, dtype, st)      \
-                            : cw_launch<KS, false, true>(p, x, w, addend, y, part, M, N, dtype, st);    \
-    return part ? cw_launch<KS, true, false>(p, x, w, addend, y, part, M, N, dtype, st)                 \
-                : cw_launch<KS, false, false>(p, x, w, addend, y, part, M, N, dtype, st);               \
-  }
-  switch (K) {
-    case 64: MRLA_CW_CALL(4)
-    case 128: MRLA_CW_CALL(8)
-    case 256: MRLA_CW_CALL(16)
-    default: return MRLA_EUNSUPPORTED;
-  }
-#undef MRLA_CW_CALL
+  return cw_instance(K, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    if (addend) return part ? cw_launch<KS, true, true>(p, x, w, addend, y, part, M, N, dtype, st)
+                            : cw_launch<KS, false, true>(p, x, w, addend, y, part, M, N, dtype, st);
+    return part ? cw_launch<KS, true, false>(p, x, w, addend, y, part, M, N, dtype, st)
+                : cw_launch<KS, false, false>(p, x, w, addend, y, part, M, N, dtype, st);
+  });
 }
 
 // y = x w^T + the compact addend [b, ceil(h/sh), ceil(w/sw), N] of a strided subsample (see conv1x1_addend.h); M = b*h*w
@@ -536,12 +495,9 @@ int launch_conv1x1_wide_sparse(const void* x, const void* w, const void* addend,
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
   const AddendGeo ag = make_addend_geo(b, h, wd, sh, sw);
-  switch (K) {
-    case 64: return cw_launch<4, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
-    case 128: return cw_launch<8, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
-    case 256: return cw_launch<16, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
-    default: return MRLA_EUNSUPPORTED;
-  }
+  return cw_instance(K, [&](auto ks) {
+    return cw_launch<decltype(ks)::value, false, true, true>(p, x, w, addend, y, nullptr, M, N, dtype, st, ag);
+  });
 }
 
 // y = T(relu?(sc * T(x w^T) + sh)): the plain forward's plan, grid and LDS, the affine applied before the tile is staged
@@ -549,12 +505,12 @@ int launch_conv1x1_wide_affine(const void* x, const void* w, const float* sc, co
                                int N, int dtype, hipStream_t st) {
   const CwPlan p = cw_plan(M, K, N);
   if (!p.groups) return MRLA_EUNSUPPORTED;
-  switch (K) {
-    case 64: return cw_launch_affine<4>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
-    case 128: return cw_launch_affine<8>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
-    case 256: return cw_launch_affine<16>(p, x, w, sc, sh, relu, y, M, N, dtype, st);
-    default: return MRLA_EUNSUPPORTED;
-  }
+  return cw_instance(K, [&](auto ks) {
+    constexpr int KS = decltype(ks)::value;
+    return launch_by_dtype(dtype, conv1x1_wide_affine_kernel<KS>, conv1x1_wide_f16_affine_kernel<KS>, cw_grid(p),
+                           dim3(kCwWaves * kWave), CwGeo<KS, false>::kLds, st, x, w, sc, sh, relu, y, M, N, p.units_per_wg,
+                           p.splits);
+  });
 }
 
 }  // namespace mrla

@@ -13,6 +13,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kWave = 64;
 constexpr int kThreads = 256;          // 4 waves per workgroup everywhere
 constexpr int kWaves = kThreads / kWave;
+constexpr int kBufFlags = 0x00020000;  // word 3 of a buffer descriptor: raw buffer, 32-bit data format (gfx9 family)
 
 // Moment record written by the forward statistics pass, per (image, channel): M_REC floats.  The sums over V and o are
 // taken about the pivots (pV, po) stored beside them -- samples of V / o from the same plane -- so that the second

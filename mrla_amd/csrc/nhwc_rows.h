@@ -29,7 +29,6 @@
 namespace mrla {
 
 constexpr unsigned kRowOob = 0x80000000u;          // byte offset no row reaches: the buffer bounds check yields zeros
-constexpr int kBufFlags = 0x00020000;              // raw buffer, 32-bit data format (gfx9 family descriptor word 3)
 
 typedef __attribute__((address_space(3))) const char* lds_cchar_ptr;
 

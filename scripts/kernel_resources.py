@@ -23,7 +23,7 @@ import tempfile
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "mrla_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-function"]           # Makefile: FLAGS
 NO_SLP = {"light_nhwc_bwd.hip", "light_nhwc_wide.hip", "light_nhwc_lean.hip", "tokens_nhwc.hip"}   # Makefile: FLAGS +=
-FIELDS = {"VGPRs": "vgprs", "AGPRs": "agprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "waves",
+FIELDS = {"VGPRs": "vgprs", "AGPRs": "agprs", "TotalSGPRs": "sgprs", "ScratchSize [bytes/lane]": "scratch", "Occupancy [waves/SIMD]": "waves",
           "LDS Size [bytes/block]": "lds"}
 _REMARK = re.compile(r"remark:\s+(.+?):\s+(\S+) \[-Rpass-analysis=kernel-resource-usage\]")
 
@@ -60,8 +60,9 @@ def parse_remarks(text):
     return kernels
 
 
-def kernel_resources(source, arch="gfx950", hipcc=None):
-    """Compile one source of mrla_amd/csrc for the device and return its kernels' figures, names demangled."""
+def kernel_resources(source, arch="gfx950", hipcc=None, csrc=CSRC):
+    """Compile one source of mrla_amd/csrc (of this checkout, or `csrc` of another) for the device and return its kernels'
+    figures, names demangled."""
     hipcc = hipcc or find_hipcc()
     if not hipcc:
         raise RuntimeError("hipcc not found (set HIPCC)")
@@ -69,7 +70,7 @@ def kernel_resources(source, arch="gfx950", hipcc=None):
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [hipcc, *flags, f"--offload-arch={arch}", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage",
                "-c", os.path.basename(source), "-o", os.path.join(tmp, "device.o")]
-        run = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True)
+        run = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
     if run.returncode != 0:
         raise RuntimeError(f"{' '.join(cmd)} failed:\n{run.stderr[-4000:]}")
     kernels = parse_remarks(run.stderr)
