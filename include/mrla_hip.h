@@ -307,8 +307,9 @@ int mrla_base_value_bwd(const void* dout, const void* x, const float* wv, const 
  *   backward: mrla_base_tail_stats_bwd (tmom: mrla_bn_moment_rows() rows) -> mrla_bn_stats_bwd -> mrla_base_attend_bwd
  *             (pmom argument = partial buffer [mrla_base_pmom_rows(), t, c]) -> mrla_base_pmom_reduce ->
  *             mrla_base_gate_bwd -> mrla_base_dv_combine -> mrla_base_value_bwd_dv
- * Supported when c % 64 == 0 and 256 % (c / (16 / sizeof(dtype))) == 0 (c a power of two up to 2048 for 16-bit types);
- * mrla_base_tile_rows returns MRLA_EUNSUPPORTED otherwise and the caller keeps the stage in MRLA_NCHW. */
+ * Supported when c % 64 == 0 and c / (16 / sizeof(dtype)) <= 256: every multiple of 64 up to 1024 (float32) / 2048 (16-bit
+ * types), DeiT's 192 / 384 / 768 included (the workgroup is the largest multiple of c / (16 / sizeof(dtype)) threads up to
+ * 256); mrla_base_tile_rows returns MRLA_EUNSUPPORTED otherwise and the caller keeps the stage in MRLA_NCHW. */
 int mrla_base_tile_rows(int b, int c, int h, int w, int dtype, int layout);
 int mrla_base_pmom_rows(int b, int c, int h, int w, int dtype, int layout);
 

@@ -178,7 +178,9 @@ def load():
 
 def check(rc, what):
     if rc != OK:
-        raise MrlaHipError(f"{what}: {_ERR.get(rc, 'error')} (code {rc})")
+        err = MrlaHipError(f"{what}: {_ERR.get(rc, 'error')} (code {rc})")
+        err.code = rc
+        raise err
 
 
 def _plan(entry, count, *args):

@@ -1063,6 +1063,11 @@ class _TokenLightFn(torch.autograd.Function):
         side = int(round((n - 1) ** 0.5))
         if side * side != n - 1 or c % d:
             raise L.MrlaHipError(f"token count {n} is not 1 + a perfect square, or c={c} not divisible by d={d}")
+        if c % 16 or c > 1024:
+            # refused here, before the statistics and gate kernels of the sequence have run for nothing: the apply kernels
+            # take 16-channel chunks (tokens.hip: chunk_for) and the statistics kernel holds a row of at most 64 * 16 channels
+            raise L.MrlaHipError(f"mrla_token_light: c={c} is not a multiple of 16 up to 1024: "
+                                 "unsupported shape/layout for the HIP kernels")
         dt, dev, st = _DT[xc.dtype], xc.device, _stream()
         p32 = [_f32(t).reshape(-1) for t in (lnx_w, lnx_b, lno_w, lno_b, wq, wk, lam)]
         wxw, wxb, wow, wob, wq32, wk32, lam32 = p32
@@ -1111,10 +1116,20 @@ class _TokenLightFn(torch.autograd.Function):
         dx, do = torch.empty_like(xc), torch.empty_like(oc)
         sums = torch.empty((c * L.TOKEN_PARTIALS + 2 * ks,), dtype=torch.float32, device=dev)
         if _seq():
-            _seq_call("mrla_token_light_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(stats), _ptr(wxw), _ptr(wxb), _ptr(wow),
-                      _ptr(wob), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32), _ptr(gate), _ptr(lam32), _ptr(mom), _ptr(dxn),
-                      _ptr(part), prow, _ptr(bmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dx), _ptr(do), _ptr(sums), b, n, c, d, res,
-                      dt, st)
+            try:
+                _seq_call("mrla_token_light_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(stats), _ptr(wxw), _ptr(wxb),
+                          _ptr(wow), _ptr(wob), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32), _ptr(gate), _ptr(lam32), _ptr(mom),
+                          _ptr(dxn), _ptr(part), prow, _ptr(bmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dx), _ptr(do), _ptr(sums),
+                          b, n, c, d, res, dt, st)
+            except L.MrlaHipError as e:
+                if getattr(e, "code", None) != L.EUNSUPPORTED:
+                    raise
+                # the sequence's first pass is the only one with a shape limit of its own: two LDS tiles of the map where
+                # c % 64 != 0 (side <= 30, while the forward's single tile serves side <= 46)
+                err = L.MrlaHipError(f"{e}: its first pass, mrla_token_apply_bwd, does not take c={c} at a "
+                                     f"{n - 1}-token map (c % 64 != 0 serves a map side of at most 30 in the backward)")
+                err.code = e.code
+                raise err from None
         else:
             _call("mrla_token_apply_bwd", xc.numel() * es * 3 + dxn.numel() * 4, _ptr(dout), _ptr(xc), _ptr(oc), _ptr(stats),
                   _ptr(wxw), _ptr(wxb), _ptr(wow), _ptr(wob), _ptr(wv32), _ptr(gate), _ptr(lam32), _ptr(dxn), _ptr(part),
