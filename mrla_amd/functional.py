@@ -6,6 +6,7 @@ a missing library raise.
 """
 import contextlib
 import ctypes
+import functools
 import threading
 import weakref
 from math import log
@@ -195,10 +196,6 @@ def _seq():
     return SEQUENCES and TIMER is None
 
 
-def _seq_call(name, *args):
-    L.call(name, *args)
-
-
 def _call(name, nbytes, *args, entry=None, alg=None, path=0):
     """Launch the C-ABI entry point `entry` (default: `name`); `name` is the label the optional timer records it under,
     with `nbytes` / `alg` / `path` as KernelTimer.summary describes them."""
@@ -319,18 +316,18 @@ def _grad_like(g, shape, stride):
     return torch.empty_strided(shape, stride, dtype=g.dtype, device=g.device).copy_(g.view(shape))
 
 
-def _on_device(fn):
-    """Run a Function.forward / backward body with the tensor argument's device current: the C ABI launches on the current
-    HIP device and on the stream handed over, while the buffers live on x.device (a model on cuda:1 in a process whose
-    current device is cuda:0 would otherwise launch on the wrong device)."""
-    import functools
-
+def _on_device(fn, at=1):
+    """Run a Function.forward / backward body (or, with at=0, a plain function of a tensor) with the device of its tensor
+    argument `at` current: the C ABI launches on the current HIP device and on the stream handed over, while the buffers
+    live on x.device (a model on cuda:1 in a process whose current device is cuda:0 would otherwise launch on the wrong
+    device)."""
     @functools.wraps(fn)
-    def wrapped(ctx, x, *args):
+    def wrapped(*args):
+        x = args[at]
         if isinstance(x, torch.Tensor) and x.is_cuda and x.device.index != torch.cuda.current_device():
             with torch.cuda.device(x.device):
-                return fn(ctx, x, *args)
-        return fn(ctx, x, *args)
+                return fn(*args)
+        return fn(*args)
     return wrapped
 
 
@@ -353,6 +350,69 @@ class _RunningStats:
             with torch.no_grad():
                 self.src[0].copy_(self.rm)
                 self.src[1].copy_(self.rv)
+
+
+def _is_fused_bn(bn):
+    """An nn.BatchNorm2d with affine parameters and tracked statistics: the norm layer the fused passes stand in for."""
+    return type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats
+
+
+def _bn_step(bn):
+    """(training, momentum) of this forward of the BatchNorm module `bn`; in train mode its batch counter is bumped
+    (bump_batch_counter, which also resolves momentum=None).  An eval-mode momentum of None is 0.0: nothing reads it."""
+    training = bn.training
+    momentum = bump_batch_counter(bn) if training else bn.momentum
+    return training, momentum or 0.0
+
+
+class _BnForward:
+    """What the forward of a node with a BatchNorm hands its statistics pass: gamma / beta as float32, the running statistics
+    (_RunningStats) and bnbuf [4, c] = scale | shift | saved mean | saved 1/sigma, which that pass fills."""
+    __slots__ = ("gamma32", "beta32", "rs", "bnbuf", "mode", "momentum", "eps")
+
+    def __init__(self, gamma, beta, running_mean, running_var, c, mode, momentum, eps, dev, what):
+        self.gamma32, self.beta32 = _f32(gamma), _f32(beta)
+        self.rs = _RunningStats(running_mean, running_var, c, what)
+        self.bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)
+        self.mode, self.momentum, self.eps = mode, float(momentum), float(eps)
+
+    def stats(self, amom, pivot, rows, c, count, st):
+        """mrla_bn_stats_fwd on `rows` partial (sum, sum^2) rows of `count` pixels each (about `pivot` where given)."""
+        bb = self.bnbuf
+        _call("mrla_bn_stats_fwd", 0, _ptr(amom), _ptr(pivot), _ptr(self.gamma32), _ptr(self.beta32), _ptr(self.rs.rm),
+              _ptr(self.rs.rv), self.mode, self.momentum, self.eps, _ptr(bb[0]), _ptr(bb[1]), _ptr(bb[2]), _ptr(bb[3]), rows, c,
+              count, st)
+
+    def stats_rows(self, records, rows, c, st):
+        """mrla_bn_stats_fwd_rows on the `rows` pivoted moment records a producer GEMM left (train mode only)."""
+        bb = self.bnbuf
+        _call("mrla_bn_stats_fwd_rows", 0, _ptr(records), _ptr(self.gamma32), _ptr(self.beta32), _ptr(self.rs.rm),
+              _ptr(self.rs.rv), L.BN_TRAIN, self.momentum, self.eps, _ptr(bb[0]), _ptr(bb[1]), _ptr(bb[2]), _ptr(bb[3]), rows, c, st)
+
+    def finish(self):
+        self.rs.finish(self.mode == L.BN_TRAIN)
+
+
+class _BnBackward:
+    """The per-channel constants of a BatchNorm backward: small [5, c] = cb[c, 3] | dgamma | dbeta.  A sequence entry point
+    takes `small` whole; stats() is the per-pass form and returns the cb view the apply pass reads."""
+    __slots__ = ("small",)
+
+    def __init__(self, c, dev):
+        self.small = torch.empty((5, c), dtype=torch.float32, device=dev)
+
+    def stats(self, tmom, gamma32, bnbuf, mode, centered, rows, c, count, st):
+        """mrla_bn_stats_bwd on `rows` partial (sum dz, sum dz*x) rows of `count` pixels each; centered: the second sum is
+        about the saved mean."""
+        s = self.small
+        cb = s[:3].view(c, 3)
+        _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), mode, centered, _ptr(cb),
+              _ptr(s[3]), _ptr(s[4]), rows, c, count, st)
+        return cb
+
+    def grads(self, dtype):
+        """(dgamma, dbeta) in the parameters' dtype."""
+        return self.small[3].to(dtype), self.small[4].to(dtype)
 
 
 def _require_cuda(x, what):
@@ -468,86 +528,61 @@ class _LightFn(torch.autograd.Function):
         mom = torch.empty((msplits, b, c, L.FWD_MOMENTS), dtype=torch.float32, device=dev)
         if cfg.fuse and (oc is None or cfg.act != L.ACT_NONE):
             raise L.MrlaHipError("the fused relu(pre + o_prev) producer needs o_prev and no activation on V")
+        nb = xc.numel() * xc.element_size()
         # inference form: nothing will be differentiated and bn_mrla does not need the batch statistics of m, so x_t is
         # neither materialised nor saved (pooling pass + an apply pass that re-forms x_t: 5N instead of 6N elements)
-        if (cfg.fuse and layout == L.NHWC and cfg.bn_mode != L.BN_TRAIN and c % 64 == 0
-                and cfg.infer):
-            psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
-            rows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)
-            part = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-            _call("mrla_light_pool_fused", xc.numel() * xc.element_size() * 2, _ptr(xc), _ptr(psc), _ptr(psh), _ptr(oc),
-                  _ptr(part), _ptr(mom), b, c, h, w, dt, layout, st)
-            gate = torch.empty((b, G), dtype=torch.float32, device=dev)
-            _call("mrla_light_gate_fwd", 0, _ptr(mom), _ptr(wq32), _ptr(wk32), ks, _ptr(gate), b, c, h * w, d, st)
-            bnbuf = None
-            if cfg.bn_mode != L.BN_NONE:
-                gamma32, beta32 = _f32(gamma), _f32(beta)
-                rs = _RunningStats(running_mean, running_var, c, "mrla light forward")
-                bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)
-                _call("mrla_light_bn_fwd", 0, _ptr(mom), _ptr(gate), _ptr(lam32), _ptr(gamma32), _ptr(beta32),
-                       _ptr(rs.rm), _ptr(rs.rv), cfg.bn_mode, float(cfg.momentum), float(cfg.eps),
-                       _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), b, c, h * w, d, st)
-            out = torch.empty_like(xc)
-            _call("mrla_light_apply_fwd_fused", xc.numel() * xc.element_size() * 3, _ptr(xc), _ptr(psc), _ptr(psh),
-                  _ptr(oc), _ptr(wv32), _ptr(gate), _ptr(bnbuf[0]) if bnbuf is not None else None,
-                  _ptr(bnbuf[1]) if bnbuf is not None else None, _ptr(lam32), _ptr(dp32), _ptr(out), b, c, h, w, d,
-                  cfg.res, dt, layout, st, path=xc.numel() * xc.element_size() * 3)
-            return out.contiguous() if via_nhwc else out
-        pre = None
+        infer = cfg.fuse and layout == L.NHWC and cfg.bn_mode != L.BN_TRAIN and c % 64 == 0 and cfg.infer
         # x_t = relu(bn3(pre) + o_prev) is re-formed by every pass that needs it instead of being stored (ABI 5)
-        lean = bool(LEAN and cfg.fuse and not via_nhwc and L.load().mrla_light_lean_supported(b, c, h, w, dt, layout) == 1)
-        nb = xc.numel() * xc.element_size()
-        if _seq():
-            psc = psh = None
-            if cfg.fuse:
-                pre, xc = xc, (None if lean else torch.empty_like(xc))
-                psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
-            gate = torch.empty((b, G), dtype=torch.float32, device=dev)
-            bnbuf = gamma32 = beta32 = rs = None
-            if cfg.bn_mode != L.BN_NONE:
-                gamma32, beta32 = _f32(gamma), _f32(beta)
-                rs = _RunningStats(running_mean, running_var, c, "mrla light forward")
-                bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
-            out = torch.empty_like(oc if lean else xc)
-            _seq_call("mrla_light_tail_fwd", _ptr(pre if cfg.fuse else xc), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wq32),
-                      _ptr(wk32), ks, _ptr(wv32), _ptr(lam32), _ptr(gamma32), _ptr(beta32),
-                      _ptr(rs.rm) if rs is not None else None, _ptr(rs.rv) if rs is not None else None, cfg.bn_mode,
-                      float(cfg.momentum), float(cfg.eps), _ptr(dp32), _ptr(mom), _ptr(xc) if (cfg.fuse and not lean) else None,
-                      _ptr(gate), _ptr(bnbuf), _ptr(out), b, c, h, w, d, cfg.res, (2 if lean else int(cfg.fuse)), dt, layout,
-                      cfg.act, st)
-            if rs is not None:
-                rs.finish(cfg.bn_mode == L.BN_TRAIN)
-        else:
-            if cfg.fuse:
-                pre, xc = xc, (None if lean else torch.empty_like(xc))
-                psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
+        lean = bool(not infer and LEAN and cfg.fuse and not via_nhwc
+                    and L.load().mrla_light_lean_supported(b, c, h, w, dt, layout) == 1)
+        pre = psc = psh = None
+        if cfg.fuse:
+            pre, xc = xc, (None if (lean or infer) else torch.empty_like(xc))
+            psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
+        gate = torch.empty((b, G), dtype=torch.float32, device=dev)
+        bn = bnbuf = gamma32 = None
+        if cfg.bn_mode != L.BN_NONE:
+            bn = _BnForward(gamma, beta, running_mean, running_var, c, cfg.bn_mode, cfg.momentum, cfg.eps, dev,
+                            "mrla light forward")
+            bnbuf, gamma32 = bn.bnbuf, bn.gamma32
+        out = torch.empty_like(oc if lean else pre if infer else xc)
+        if not infer and _seq():
+            L.call("mrla_light_tail_fwd", _ptr(pre if cfg.fuse else xc), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wq32), _ptr(wk32),
+                   ks, _ptr(wv32), _ptr(lam32), _ptr(gamma32), _ptr(bn.beta32) if bn is not None else None,
+                   _ptr(bn.rs.rm) if bn is not None else None, _ptr(bn.rs.rv) if bn is not None else None, cfg.bn_mode,
+                   float(cfg.momentum), float(cfg.eps), _ptr(dp32), _ptr(mom), _ptr(xc) if (cfg.fuse and not lean) else None,
+                   _ptr(gate), _ptr(bnbuf), _ptr(out), b, c, h, w, d, cfg.res, (2 if lean else int(cfg.fuse)), dt, layout,
+                   cfg.act, st)
+        else:                       # one call per pass (the inference form has no sequence entry point)
+            if infer:
+                rows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)
+                part = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
+                _call("mrla_light_pool_fused", nb * 2, _ptr(pre), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(part), _ptr(mom), b, c, h,
+                      w, dt, layout, st)
+            elif cfg.fuse:
                 _call("mrla_light_stats_fwd_fused", nb * (2 if lean else 3), _ptr(pre), _ptr(psc), _ptr(psh),
                       _ptr(oc), _ptr(wv32), _ptr(mom), _ptr(xc), b, c, h, w, dt, layout, st)
             else:
-                _call("mrla_light_stats_fwd", xc.numel() * xc.element_size() * (2 if oc is not None else 1), _ptr(xc),
-                      _ptr(oc), _ptr(wv32), _ptr(mom), b, c, h, w, dt, layout, cfg.act, st)
-            gate = torch.empty((b, G), dtype=torch.float32, device=dev)
+                _call("mrla_light_stats_fwd", nb * (2 if oc is not None else 1), _ptr(xc), _ptr(oc), _ptr(wv32), _ptr(mom), b, c,
+                      h, w, dt, layout, cfg.act, st)
             _call("mrla_light_gate_fwd", 0, _ptr(mom), _ptr(wq32), _ptr(wk32), ks, _ptr(gate), b, c, h * w, d, st)
-            bnbuf = gamma32 = None
-            if cfg.bn_mode != L.BN_NONE:
-                gamma32, beta32 = _f32(gamma), _f32(beta)
-                rs = _RunningStats(running_mean, running_var, c, "mrla light forward")
-                bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
-                _call("mrla_light_bn_fwd", 0, _ptr(mom), _ptr(gate), _ptr(lam32), _ptr(gamma32), _ptr(beta32),
-                       _ptr(rs.rm), _ptr(rs.rv), cfg.bn_mode, float(cfg.momentum), float(cfg.eps),
-                       _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), b, c, h * w, d, st)
-                rs.finish(cfg.bn_mode == L.BN_TRAIN)
-            if lean:
-                out = torch.empty_like(oc)
-                _call("mrla_light_apply_fwd_fused", nb * 3, _ptr(pre), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wv32), _ptr(gate),
-                      _ptr(bnbuf[0]) if bnbuf is not None else None, _ptr(bnbuf[1]) if bnbuf is not None else None,
-                      _ptr(lam32), _ptr(dp32), _ptr(out), b, c, h, w, d, cfg.res, dt, layout, st, path=nb * 3)
+            sc = sh = None
+            if bn is not None:
+                _call("mrla_light_bn_fwd", 0, _ptr(mom), _ptr(gate), _ptr(lam32), _ptr(gamma32), _ptr(bn.beta32), _ptr(bn.rs.rm),
+                      _ptr(bn.rs.rv), cfg.bn_mode, bn.momentum, bn.eps, _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]),
+                      _ptr(bnbuf[3]), b, c, h * w, d, st)
+                sc, sh = _ptr(bnbuf[0]), _ptr(bnbuf[1])
+            if lean or infer:       # the apply pass that re-forms x_t from pre
+                _call("mrla_light_apply_fwd_fused", nb * 3, _ptr(pre), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wv32), _ptr(gate), sc,
+                      sh, _ptr(lam32), _ptr(dp32), _ptr(out), b, c, h, w, d, cfg.res, dt, layout, st, path=nb * 3)
             else:
-                out = torch.empty_like(xc)
                 _call("mrla_light_apply_fwd", nb * (3 if oc is not None else 2), _ptr(xc), _ptr(oc), _ptr(wv32), _ptr(gate),
-                      _ptr(bnbuf[0]) if bnbuf is not None else None, _ptr(bnbuf[1]) if bnbuf is not None else None,
-                      _ptr(lam32), _ptr(dp32), _ptr(out), b, c, h, w, d, cfg.res, dt, layout, cfg.act, st,
+                      sc, sh, _ptr(lam32), _ptr(dp32), _ptr(out), b, c, h, w, d, cfg.res, dt, layout, cfg.act, st,
                       path=nb * (3 if oc is not None else 2))
+        if infer:                   # (nothing is saved: there is no backward)
+            return out.contiguous() if via_nhwc else out
+        if bn is not None:
+            bn.finish()
 
         ctx.cfg, ctx.layout, ctx.ks = cfg, layout, ks
         ctx.shapes = (wq.shape, wk.shape, wv.shape, lam.shape if lam is not None else None)
@@ -583,78 +618,59 @@ class _LightFn(torch.autograd.Function):
         # (partial records of the backward statistics pass: > 1 only for few, large images -- detection batches)
         splits = L.load().mrla_light_bmom_splits(b, c, h, w, dt, layout)
         L.check(min(splits, 0), "mrla_light_bmom_splits")
+        bmom = torch.empty((splits, b, c, L.BWD_MOMENTS), dtype=torch.float32, device=dev)
+        small = torch.empty((11, c), dtype=torch.float32, device=dev)     # cb[c,4] | dgamma | dbeta | dlam | cb_lo[c,4]
+        dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
+        dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
+        rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
+        L.check(min(rows, 0), "mrla_light_wgrad_rows")
+        dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(like)
+        do = torch.empty_like(oc) if oc is not None else None
+        # the deferred bn3's backward sums (sum dpre, sum dpre*y3) ride in the apply pass: one more row fetch, no 2N pass
+        pre_tmom = center = None
+        if ctx.pre_sums and pre is not None:
+            pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
+            center = _ptr(cfg.pre_box.center)
+        elif not lean:
+            pre = None
+        wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
         if _seq():
-            bmom = torch.empty((splits, b, c, L.BWD_MOMENTS), dtype=torch.float32, device=dev)
-            small = torch.empty((11, c), dtype=torch.float32, device=dev)     # cb[c,4] | dgamma | dbeta | dlam | cb_lo[c,4]
-            dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
-            dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
-            rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
-            L.check(min(rows, 0), "mrla_light_wgrad_rows")
-            dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
-            dx = torch.empty_like(like)
-            do = torch.empty_like(oc) if oc is not None else None
-            pre_tmom = None
-            if ctx.pre_sums and pre is not None:
-                pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-            elif not lean:
-                pre = None
-            wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
-            _seq_call("mrla_light_tail_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32),
-                      _ptr(lam32), _ptr(gamma32) if has_bn else None, _ptr(dp32), _ptr(mom), _ptr(gate),
-                      _ptr(bnbuf) if has_bn else None, cfg.bn_mode, _ptr(bmom), _ptr(small), _ptr(dyx), _ptr(dwqk_part),
-                      _ptr(dwv_part), rows, _ptr(dx), _ptr(do), _ptr(pre), _ptr(psc), _ptr(psh),
-                      _ptr(cfg.pre_box.center) if pre_tmom is not None else None, _ptr(pre_tmom), _ptr(wsum), b, c, h, w, d,
-                      cfg.res, int(cfg.fuse), dt, layout, cfg.act, st)
-            if pre_tmom is not None:
-                cfg.pre_box.put(dx, pre_tmom, rows)
+            L.call("mrla_light_tail_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32), _ptr(lam32),
+                   _ptr(gamma32) if has_bn else None, _ptr(dp32), _ptr(mom), _ptr(gate), _ptr(bnbuf) if has_bn else None,
+                   cfg.bn_mode, _ptr(bmom), _ptr(small), _ptr(dyx), _ptr(dwqk_part), _ptr(dwv_part), rows, _ptr(dx), _ptr(do),
+                   _ptr(pre), _ptr(psc), _ptr(psh), center, _ptr(pre_tmom), _ptr(wsum), b, c, h, w, d, cfg.res, int(cfg.fuse),
+                   dt, layout, cfg.act, st)
         else:
-            bmom = torch.empty((splits, b, c, L.BWD_MOMENTS), dtype=torch.float32, device=dev)
             if lean:
                 _call("mrla_light_stats_bwd_fused", nb * 3, _ptr(dout), _ptr(pre), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wv32),
                       _ptr(mom), _ptr(bmom), b, c, h, w, dt, layout, st)
             else:
                 _call("mrla_light_stats_bwd", nb * (3 if oc is not None else 2), _ptr(dout), _ptr(xc), _ptr(oc), _ptr(wv32),
                       _ptr(mom), _ptr(bmom), b, c, h, w, dt, layout, cfg.act, st)
-            small = torch.empty((11, c), dtype=torch.float32, device=dev)     # cb[c,4] | dgamma | dbeta | dlam | cb_lo[c,4]
             cb, cb_lo = small[:4].view(c, 4), small[7:].view(c, 4)
-            has_bn = cfg.bn_mode != L.BN_NONE
             _call("mrla_light_bn_bwd", 0, _ptr(mom), _ptr(bmom), _ptr(gate), _ptr(lam32), _ptr(gamma32) if has_bn else None,
                    _ptr(dp32), _ptr(bnbuf[2]) if has_bn else None, _ptr(bnbuf[3]) if has_bn else None, cfg.bn_mode,
                    _ptr(cb), _ptr(cb_lo), _ptr(small[4]) if has_bn else None, _ptr(small[5]) if has_bn else None,
                    _ptr(small[6]) if lam32 is not None else None, b, c, h * w, d, st)
-            dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
-            dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
             _call("mrla_light_gate_bwd", 0, _ptr(mom), _ptr(bmom), _ptr(gate), _ptr(cb), _ptr(cb_lo), _ptr(dp32), _ptr(wq32),
                    _ptr(wk32), ks, _ptr(dyx), _ptr(dwqk_part), b, c, h * w, d, st)
-            rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
-            L.check(min(rows, 0), "mrla_light_wgrad_rows")
-            dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
-            dx = torch.empty_like(like)
-            do = torch.empty_like(oc) if oc is not None else None
-            # the deferred bn3's backward sums (sum dpre, sum dpre*y3) ride in this pass: one more row fetch, no 2N pass
-            pre_tmom = None
-            if ctx.pre_sums and pre is not None:
-                pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-            elif not lean:
-                pre = None
             if lean:
                 # dOut, y3, o_prev in; dx, do out: section 8(d)'s five passes exactly (x_t is re-formed, bn3's sums ride along)
                 _call("mrla_light_apply_bwd", nb * 5, _ptr(dout), _ptr(pre), _ptr(psc), _ptr(psh), _ptr(oc), _ptr(wv32),
                       _ptr(gate), _ptr(cb), _ptr(lam32), _ptr(dp32), _ptr(dyx), _ptr(dx), _ptr(do), _ptr(dwv_part),
-                      _ptr(cfg.pre_box.center) if pre_tmom is not None else None, _ptr(pre_tmom), b, c, h, w, d, cfg.res, dt,
-                      layout, st, entry="mrla_light_apply_bwd_fused", alg=nb * 5, path=nb * 5)
+                      center, _ptr(pre_tmom), b, c, h, w, d, cfg.res, dt, layout, st, entry="mrla_light_apply_bwd_fused",
+                      alg=nb * 5, path=nb * 5)
             else:
                 _call("mrla_light_apply_bwd", nb * ((5 if oc is not None else 3) + (pre is not None)),
                       _ptr(dout), _ptr(xc), _ptr(oc), _ptr(wv32), _ptr(gate), _ptr(cb), _ptr(lam32),
-                      _ptr(dp32), _ptr(dyx), _ptr(dx), _ptr(do), _ptr(dwv_part), _ptr(pre),
-                      _ptr(cfg.pre_box.center) if pre is not None else None, _ptr(pre_tmom), b, c, h, w, d, cfg.res,
-                      int(cfg.fuse), dt, layout, cfg.act, st,
+                      _ptr(dp32), _ptr(dyx), _ptr(dx), _ptr(do), _ptr(dwv_part), _ptr(pre), center, _ptr(pre_tmom), b, c, h, w,
+                      d, cfg.res, int(cfg.fuse), dt, layout, cfg.act, st,
                       # section 8(d): dOut, x_t, o_prev in; dx, do out (the y3 row read for bn3's folded sums is not in that count)
                       alg=nb * (5 if oc is not None else 3), path=nb * (5 if oc is not None else 3))
-            if pre_tmom is not None:
-                cfg.pre_box.put(dx, pre_tmom, rows)
-            wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
             _call("mrla_reduce_rows2", 0, _ptr(dwv_part), _ptr(wsum), rows, c * 9, _ptr(dwqk_part), _ptr(wsum[c * 9:]), b, 2 * ks, st)
+        if pre_tmom is not None:
+            cfg.pre_box.put(dx, pre_tmom, rows)
 
         sq, sk, sv, sl = ctx.shapes
         tq, tk, tv, tl, tg = ctx.pdtypes
@@ -683,17 +699,14 @@ def mrla_light(x, wq, wk, wv, d, o_prev=None, lam=None, bn=None, dp=None, res=Fa
     if bn is not None:
         tensors += [bn["weight"], bn["bias"]]
     infer = not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))
-    if bn is None:
-        cfg = LightConfig(d, L.BN_NONE, res=int(res), act=L.ACT_GELU if act_gelu else L.ACT_NONE, fuse=pre_activation,
-                          pre_affine=pre_affine, pre_box=pre_box)
-        cfg.infer = infer
-        return _LightFn.apply(x, o_prev, wq, wk, wv, lam, None, None, None, None, dp, cfg)
-    cfg = LightConfig(d, L.BN_TRAIN if bn["training"] else L.BN_EVAL, bn.get("momentum", 0.1), bn.get("eps", 1e-5),
-                      int(res), L.ACT_GELU if act_gelu else L.ACT_NONE, fuse=pre_activation, pre_affine=pre_affine,
-                      pre_box=pre_box)
+    mode, bnp = L.BN_NONE, {}
+    if bn is not None:
+        mode, bnp = (L.BN_TRAIN if bn["training"] else L.BN_EVAL), bn
+    cfg = LightConfig(d, mode, bnp.get("momentum", 0.1), bnp.get("eps", 1e-5), int(res), L.ACT_GELU if act_gelu else L.ACT_NONE,
+                      fuse=pre_activation, pre_affine=pre_affine, pre_box=pre_box)
     cfg.infer = infer
-    return _LightFn.apply(x, o_prev, wq, wk, wv, lam, bn["weight"], bn["bias"], bn["running_mean"], bn["running_var"],
-                          dp, cfg)
+    return _LightFn.apply(x, o_prev, wq, wk, wv, lam, bnp.get("weight"), bnp.get("bias"), bnp.get("running_mean"),
+                          bnp.get("running_var"), dp, cfg)
 
 
 # ======================================================================================================
@@ -833,75 +846,54 @@ class _BaseFn(torch.autograd.Function):
                           device=dev)
         nhwc = layout == L.NHWC
         es = xc.element_size()
+        idc = pre = None
+        if cfg.fuse:                # x is the pre-activation: x_t = relu(x + identity) is formed by the pooling pass
+            idc = _layout_of(identity, layout)[1]
+            pre, xc = xc, torch.empty_like(xc)
+        psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)      # (NHWC stages only: mrla_base)
+        q = torch.empty((b, c), dtype=torch.float32, device=dev)
+        attn = torch.empty_like(xc)
+        arows = L.load().mrla_base_tile_rows(b, c, h, w, dt, layout)      # rows of the (sum, sum^2) partials
+        L.check(min(arows, 0), "mrla_base_tile_rows")
+        amom = torch.empty((arows, c, 2), dtype=torch.float32, device=dev)
+        bn = bnbuf = gamma32 = None
+        out = attn
+        if cfg.tail:
+            bn = _BnForward(gamma, beta, running_mean, running_var, c, cfg.bn_mode, cfg.momentum, cfg.eps, dev,
+                            "mrla base forward")
+            bnbuf, gamma32 = bn.bnbuf, bn.gamma32
+            out = torch.empty_like(xc)
         if nhwc and _seq():     # the whole layer + tail: one call (mrla_base_layer_fwd)
-            idc = pre = None
-            if cfg.fuse:
-                idc = _layout_of(identity, layout)[1]
-                pre, xc = xc, torch.empty_like(xc)
-            psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
-            q = torch.empty((b, c), dtype=torch.float32, device=dev)
-            attn = torch.empty_like(xc)
-            arows = L.load().mrla_base_tile_rows(b, c, h, w, dt, layout)
-            L.check(min(arows, 0), "mrla_base_tile_rows")
-            amom = torch.empty((arows, c, 2), dtype=torch.float32, device=dev)
-            bnbuf = gamma32 = beta32 = rs = None
-            out = attn
-            if cfg.tail:
-                gamma32, beta32 = _f32(gamma), _f32(beta)
-                rs = _RunningStats(running_mean, running_var, c, "mrla base forward")
-                bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)
-                out = torch.empty_like(xc)
-            _seq_call("mrla_base_layer_fwd", _ptr(pre if cfg.fuse else xc), _ptr(psc), _ptr(psh), _ptr(idc), _ptr(wq32),
-                      _ptr(wk32), ks, _ptr(wv32), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm) if rs is not None else None,
-                      _ptr(rs.rv) if rs is not None else None, cfg.bn_mode if cfg.tail else L.BN_NONE, float(cfg.momentum),
-                      float(cfg.eps), _ptr(dp32), _ptr(mom), _ptr(xc) if cfg.fuse else None, _ptr(stage.V), _ptr(stage.K),
-                      _ptr(stage.P), _ptr(q), _ptr(attn), _ptr(amom), arows, _ptr(bnbuf), _ptr(out) if cfg.tail else None,
-                      int(cfg.tail), b, c, h, w, d, T, t, dt, st)
-            if rs is not None:
-                rs.finish(cfg.bn_mode == L.BN_TRAIN)
-            stage.t = t
+            L.call("mrla_base_layer_fwd", _ptr(pre if cfg.fuse else xc), _ptr(psc), _ptr(psh), _ptr(idc), _ptr(wq32),
+                   _ptr(wk32), ks, _ptr(wv32), _ptr(gamma32), _ptr(bn.beta32) if bn is not None else None,
+                   _ptr(bn.rs.rm) if bn is not None else None, _ptr(bn.rs.rv) if bn is not None else None,
+                   cfg.bn_mode if cfg.tail else L.BN_NONE, float(cfg.momentum), float(cfg.eps), _ptr(dp32), _ptr(mom),
+                   _ptr(xc) if cfg.fuse else None, _ptr(stage.V), _ptr(stage.K), _ptr(stage.P), _ptr(q), _ptr(attn), _ptr(amom),
+                   arows, _ptr(bnbuf), _ptr(out) if cfg.tail else None, int(cfg.tail), b, c, h, w, d, T, t, dt, st)
         else:
+            nb = xc.numel() * es
             if nhwc:                # one pass: pooling moments, V_t -> ring slot (and x_t = relu(x + identity) when fused)
-                idc = pre = None
-                if cfg.fuse:
-                    idc = _layout_of(identity, layout)[1]
-                    pre, xc = xc, torch.empty_like(xc)
-                psc, psh = cfg.pre_affine if cfg.pre_affine is not None else (None, None)
-                _call("mrla_base_pool_value_fwd", xc.numel() * es * (4 if cfg.fuse else 2), _ptr(pre if cfg.fuse else xc),
+                _call("mrla_base_pool_value_fwd", nb * (4 if cfg.fuse else 2), _ptr(pre if cfg.fuse else xc),
                       _ptr(psc), _ptr(psh), _ptr(idc), _ptr(wv32), _ptr(mom), _ptr(xc) if cfg.fuse else None,
-                      _ptr(stage.V[t - 1]), b, c, h, w, dt, layout, st, path=xc.numel() * es * 2)
-            elif cfg.fuse:          # x is the pre-activation: x_t = relu(x + identity) formed by the pooling pass
-                idc = _layout_of(identity, L.NCHW)[1]
-                pre, xc = xc, torch.empty_like(xc)
-                _call("mrla_light_stats_fwd_fused", xc.numel() * xc.element_size() * 3, _ptr(pre), None, None, _ptr(idc),
+                      _ptr(stage.V[t - 1]), b, c, h, w, dt, layout, st, path=nb * 2)
+            elif cfg.fuse:
+                _call("mrla_light_stats_fwd_fused", nb * 3, _ptr(pre), None, None, _ptr(idc),
                       _ptr(wv32), _ptr(mom), _ptr(xc), b, c, h, w, dt, layout, st)
             else:
-                _call("mrla_light_stats_fwd", xc.numel() * xc.element_size(), _ptr(xc), None, _ptr(wv32), _ptr(mom), b, c, h,
+                _call("mrla_light_stats_fwd", nb, _ptr(xc), None, _ptr(wv32), _ptr(mom), b, c, h,
                       w, dt, layout, L.ACT_NONE, st)
-            q = torch.empty((b, c), dtype=torch.float32, device=dev)
             _call("mrla_base_gate_fwd", 0, _ptr(mom), _ptr(wq32), _ptr(wk32), ks, _ptr(stage.K), _ptr(stage.P), _ptr(q), b, c,
                    h * w, d, T, t, st)
-            attn = torch.empty_like(xc)
-            arows = L.load().mrla_base_tile_rows(b, c, h, w, dt, layout)      # rows of the (sum, sum^2) partials
-            L.check(min(arows, 0), "mrla_base_tile_rows")
-            amom = torch.empty((arows, c, 2), dtype=torch.float32, device=dev)
-            _call("mrla_base_attend_fwd", xc.numel() * es * ((t + 1) if nhwc else (t + 2)), None if nhwc else _ptr(xc),
+            _call("mrla_base_attend_fwd", nb * ((t + 1) if nhwc else (t + 2)), None if nhwc else _ptr(xc),
                   _ptr(wv32), _ptr(stage.V), _ptr(stage.P), _ptr(attn), _ptr(amom), b, c, h, w, d, T, t, dt, layout, st,
-                  path=xc.numel() * es * (t - 1 if nhwc else t + 1))      # section 8(d): (t + 2) N per layer with the value pass + tail
-            stage.t = t
-            bnbuf = gamma32 = None
-            out = attn
+                  path=nb * (t - 1 if nhwc else t + 1))      # section 8(d): (t + 2) N per layer with the value pass + tail
             if cfg.tail:
-                gamma32, beta32 = _f32(gamma), _f32(beta)
-                rs = _RunningStats(running_mean, running_var, c, "mrla base forward")
-                bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)
-                _call("mrla_bn_stats_fwd", 0, _ptr(amom), None, _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
-                       cfg.bn_mode, float(cfg.momentum), float(cfg.eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]),
-                       _ptr(bnbuf[3]), arows, c, b * h * w // arows, st)
-                rs.finish(cfg.bn_mode == L.BN_TRAIN)
-                out = torch.empty_like(xc)
-                _call("mrla_base_tail_fwd", xc.numel() * xc.element_size() * 3, _ptr(xc), _ptr(attn), _ptr(bnbuf[0]),
-                      _ptr(bnbuf[1]), _ptr(dp32), _ptr(out), b, c, h, w, dt, layout, st, path=xc.numel() * xc.element_size())
+                bn.stats(amom, None, arows, c, b * h * w // arows, st)
+                _call("mrla_base_tail_fwd", nb * 3, _ptr(xc), _ptr(attn), _ptr(bnbuf[0]),
+                      _ptr(bnbuf[1]), _ptr(dp32), _ptr(out), b, c, h, w, dt, layout, st, path=nb)
+        stage.t = t
+        if bn is not None:
+            bn.finish()
         ctx.cfg, ctx.layout, ctx.ks, ctx.stage, ctx.t = cfg, layout, ks, stage, t
         ctx.shapes = (wq.shape, wk.shape, wv.shape)
         ctx.wv_stride = wv.stride()
@@ -931,97 +923,72 @@ class _BaseFn(torch.autograd.Function):
         Tc = stage.bwd_top            # later layers that received no gradient in this pass left no dA slot behind
         es = xc.element_size()
 
-        if nhwc and _seq():     # the whole layer + tail backward: one call (mrla_base_layer_bwd)
-            dgamma = dbeta = small = tmom = None
-            trows = 1
-            if cfg.tail:
-                trows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)
-                tmom = torch.empty((trows, c, 2), dtype=torch.float32, device=dev)
-                small = torch.empty((5, c), dtype=torch.float32, device=dev)         # cb[c,3] | dgamma | dbeta
-            pmom = torch.empty((b, c, t), dtype=torch.float32, device=dev)
+        nb = xc.numel() * es
+        kb = tmom = None
+        trows = 1
+        if cfg.tail:
+            trows = L.load().mrla_bn_moment_rows(b, c, h, w, layout) if nhwc else b
+            tmom = torch.empty((trows, c, 2), dtype=torch.float32, device=dev)
+            kb = _BnBackward(c, dev)
+        pmom = torch.empty((b, c, t), dtype=torch.float32, device=dev)
+        ppart, prows = pmom, 0                       # (the NCHW pass leaves <dA_t, V_j> in pmom itself)
+        dv = pre_tmom = center = None
+        if nhwc:
             prows = L.load().mrla_base_pmom_rows(b, c, h, w, dt, layout)
             L.check(min(prows, 0), "mrla_base_pmom_rows")
             ppart = torch.empty((prows, t, c), dtype=torch.float32, device=dev)
-            dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
-            dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
-            rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
-            L.check(min(rows, 0), "mrla_light_wgrad_rows")
-            dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
-            dx = torch.empty_like(xc)
-            dv = torch.empty((b, h, w, c), dtype=xc.dtype, device=dev)
-            res = int(cfg.tail) | (2 if cfg.fuse else 0)
-            pre_tmom = None
-            if pre is not None:
-                pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-            else:
-                pre = None
-            wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
-            _seq_call("mrla_base_layer_bwd", _ptr(dout), _ptr(xc), _ptr(attn), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32),
-                      _ptr(gamma32), _ptr(dp32), _ptr(mom), _ptr(q), _ptr(bnbuf), cfg.bn_mode if cfg.tail else L.BN_NONE,
-                      _ptr(stage.V), _ptr(stage.dA), _ptr(stage.K), _ptr(stage.dK), _ptr(stage.P), _ptr(tmom), trows,
-                      _ptr(small), _ptr(ppart), prows, _ptr(pmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dv), _ptr(dwv_part), rows,
-                      _ptr(dx), _ptr(pre), _ptr(cfg.pre_box.center) if pre is not None else None, _ptr(pre_tmom), _ptr(wsum),
-                      int(cfg.tail), int(first), res, b, c, h, w, d, T, t, Tc, dt, st)
-            if pre_tmom is not None:
-                cfg.pre_box.put(dx, pre_tmom, rows)
-            if cfg.tail:
-                dgamma, dbeta = small[3].to(ctx.pdtypes[3]), small[4].to(ctx.pdtypes[3])
+            dv = torch.empty((b, h, w, c), dtype=xc.dtype, device=dev)      # dV_t from the dA slots t..Tc
+        dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
+        dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
+        rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
+        L.check(min(rows, 0), "mrla_light_wgrad_rows")
+        dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(xc)
+        res = int(cfg.tail) | (2 if cfg.fuse else 0)
+        if pre is not None:
+            # the deferred bn3's backward sums (sum dpre, sum dpre*(y3 - mean)) ride in the value pass: one more row fetch, no 2N pass
+            pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
+            center = _ptr(cfg.pre_box.center)
+        wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
+        if nhwc and _seq():     # the whole layer + tail backward: one call (mrla_base_layer_bwd)
+            L.call("mrla_base_layer_bwd", _ptr(dout), _ptr(xc), _ptr(attn), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32),
+                   _ptr(gamma32), _ptr(dp32), _ptr(mom), _ptr(q), _ptr(bnbuf), cfg.bn_mode if cfg.tail else L.BN_NONE,
+                   _ptr(stage.V), _ptr(stage.dA), _ptr(stage.K), _ptr(stage.dK), _ptr(stage.P), _ptr(tmom), trows,
+                   _ptr(kb.small) if cfg.tail else None, _ptr(ppart), prows, _ptr(pmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dv),
+                   _ptr(dwv_part), rows, _ptr(dx), _ptr(pre), center, _ptr(pre_tmom), _ptr(wsum),
+                   int(cfg.tail), int(first), res, b, c, h, w, d, T, t, Tc, dt, st)
         else:
-            cb = dgamma = dbeta = None
+            cb = None
             if cfg.tail:
-                trows = L.load().mrla_bn_moment_rows(b, c, h, w, layout) if nhwc else b
-                tmom = torch.empty((trows, c, 2), dtype=torch.float32, device=dev)
-                center = bnbuf[2] if nhwc else None      # sums about the saved batch mean (the NCHW slab kernel keeps raw sums)
-                _call("mrla_base_tail_stats_bwd", xc.numel() * es * 2, _ptr(dout), _ptr(attn), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
-                      _ptr(center), _ptr(dp32), _ptr(tmom), b, c, h, w, dt, layout, st)
-                small = torch.empty((5, c), dtype=torch.float32, device=dev)         # cb[c,3] | dgamma | dbeta
-                cb = small[:3].view(c, 3)
-                _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), cfg.bn_mode,
-                       int(center is not None), _ptr(cb), _ptr(small[3]), _ptr(small[4]), trows, c, b * h * w // trows, st)
-                dgamma, dbeta = small[3].to(ctx.pdtypes[3]), small[4].to(ctx.pdtypes[3])
-            pmom = torch.empty((b, c, t), dtype=torch.float32, device=dev)
-            prows = L.load().mrla_base_pmom_rows(b, c, h, w, dt, layout)
-            ppart = torch.empty((prows, t, c), dtype=torch.float32, device=dev) if nhwc else pmom
+                center_mean = bnbuf[2] if nhwc else None      # sums about the saved batch mean (the NCHW slab kernel keeps raw sums)
+                _call("mrla_base_tail_stats_bwd", nb * 2, _ptr(dout), _ptr(attn), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
+                      _ptr(center_mean), _ptr(dp32), _ptr(tmom), b, c, h, w, dt, layout, st)
+                cb = kb.stats(tmom, gamma32, bnbuf, cfg.bn_mode, int(nhwc), trows, c, b * h * w // trows, st)
             # (t + 3) N of streams + the fp32 partial rows of <dA_t, V_j> (one row of t x c floats per 16-pixel tile: 2 / 16 of the
             # V bytes it reads -- the "9 %" the PMC pass sees above (t + 3) N; mrla_base_pmom_reduce reads them back)
-            _call("mrla_base_attend_bwd", xc.numel() * es * (t + 3) + (ppart.numel() * 4 if nhwc else 0), _ptr(dout), _ptr(attn),
+            _call("mrla_base_attend_bwd", nb * (t + 3) + (ppart.numel() * 4 if nhwc else 0), _ptr(dout), _ptr(attn),
                   _ptr(bnbuf[0]) if cfg.tail else None, _ptr(bnbuf[1]) if cfg.tail else None, _ptr(dp32), _ptr(cb),
                   _ptr(stage.V), _ptr(stage.dA), _ptr(ppart), b, c, h, w, T, t, dt, layout, st,
-                  alg=xc.numel() * es * (t + 3),
-                  path=xc.numel() * es * (t + 1))                         # section 8(d): ~(2t + 3) N per layer, backward
+                  alg=nb * (t + 3),
+                  path=nb * (t + 1))                         # section 8(d): ~(2t + 3) N per layer, backward
             if nhwc:
                 _call("mrla_base_pmom_reduce", (ppart.numel() + pmom.numel()) * 4, _ptr(ppart), _ptr(pmom), b, c, t, prows, st)
-            dyx = torch.empty((b, c), dtype=torch.float32, device=dev)
-            dwqk_part = torch.empty((b, 2 * ks), dtype=torch.float32, device=dev)
             _call("mrla_base_gate_bwd", 0, _ptr(mom), _ptr(pmom), _ptr(stage.P), _ptr(q), _ptr(stage.K), _ptr(stage.dK),
                    _ptr(wq32), _ptr(wk32), ks, _ptr(dyx), _ptr(dwqk_part), b, c, h * w, d, T, t, int(first), st)
-            rows = L.load().mrla_light_wgrad_rows(b, c, h, w, dt, layout)
-            L.check(min(rows, 0), "mrla_light_wgrad_rows")
-            dwv_part = torch.empty((rows, c * 9), dtype=torch.float32, device=dev)
-            dx = torch.empty_like(xc)
-            res = int(cfg.tail) | (2 if cfg.fuse else 0)
             if nhwc:                # dV_t from the dA slots t..Tc, then the transposed 3x3 pass
-                dv = torch.empty((b, h, w, c), dtype=xc.dtype, device=dev)
-                _call("mrla_base_dv_combine", xc.numel() * es * (Tc - t + 2), _ptr(stage.dA), _ptr(stage.P), _ptr(dv),
-                      b, c, h, w, d, T, t, Tc, dt, layout, st, path=xc.numel() * es * (Tc - t + 1))
-                # the deferred bn3's backward sums (sum dpre, sum dpre*(y3 - mean)) ride in this pass: one more row fetch, no 2N pass
-                pre_tmom = None
-                if pre is not None:
-                    pre_tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-                else:
-                    pre = None
-                _call("mrla_base_value_bwd_dv", xc.numel() * es * (4 + (pre is not None)), _ptr(dout), _ptr(xc), _ptr(wv32),
-                      _ptr(dv), _ptr(dyx), _ptr(dx), _ptr(dwv_part), _ptr(pre),
-                      _ptr(cfg.pre_box.center) if pre is not None else None, _ptr(pre_tmom), b, c, h, w, res, dt, layout, st,
-                      alg=xc.numel() * es * 4, path=xc.numel() * es)
-                if pre_tmom is not None:
-                    cfg.pre_box.put(dx, pre_tmom, rows)
+                _call("mrla_base_dv_combine", nb * (Tc - t + 2), _ptr(stage.dA), _ptr(stage.P), _ptr(dv),
+                      b, c, h, w, d, T, t, Tc, dt, layout, st, path=nb * (Tc - t + 1))
+                _call("mrla_base_value_bwd_dv", nb * (4 + (pre is not None)), _ptr(dout), _ptr(xc), _ptr(wv32),
+                      _ptr(dv), _ptr(dyx), _ptr(dx), _ptr(dwv_part), _ptr(pre), center, _ptr(pre_tmom), b, c, h, w, res, dt,
+                      layout, st, alg=nb * 4, path=nb)
             else:
-                _call("mrla_base_value_bwd", xc.numel() * es * (Tc - t + 4), _ptr(dout), _ptr(xc), _ptr(wv32),
+                _call("mrla_base_value_bwd", nb * (Tc - t + 4), _ptr(dout), _ptr(xc), _ptr(wv32),
                       _ptr(stage.dA), _ptr(stage.P), _ptr(dyx), _ptr(dx), _ptr(dwv_part), b, c, h, w, d, T, t, Tc, res, dt,
-                      layout, st, path=xc.numel() * es * (Tc - t + 2))
-            wsum = torch.empty((c * 9 + 2 * ks,), dtype=torch.float32, device=dev)
+                      layout, st, path=nb * (Tc - t + 2))
             _call("mrla_reduce_rows2", 0, _ptr(dwv_part), _ptr(wsum), rows, c * 9, _ptr(dwqk_part), _ptr(wsum[c * 9:]), b, 2 * ks, st)
+        if pre_tmom is not None:
+            cfg.pre_box.put(dx, pre_tmom, rows)
+        dgamma, dbeta = kb.grads(ctx.pdtypes[3]) if cfg.tail else (None, None)
         sq, sk, sv = ctx.shapes
         tq, tk, tv, _ = ctx.pdtypes
         return (dx, dx if cfg.fuse else None, wsum[c * 9:c * 9 + ks].view(sq).to(tq), wsum[c * 9 + ks:].view(sk).to(tk),
@@ -1078,9 +1045,9 @@ class _TokenLightFn(torch.autograd.Function):
         gate = torch.empty((b, c // d), dtype=torch.float32, device=dev)
         out = torch.empty_like(xc)
         if _seq():
-            _seq_call("mrla_token_light_fwd", _ptr(xc), _ptr(oc), _ptr(wxw), _ptr(wxb), _ptr(wow), _ptr(wob), _ptr(wq32),
-                      _ptr(wk32), ks, _ptr(wv32), _ptr(lam32), float(eps), _ptr(stats), _ptr(mom), _ptr(gate), _ptr(out), b, n,
-                      c, d, int(res), dt, st)
+            L.call("mrla_token_light_fwd", _ptr(xc), _ptr(oc), _ptr(wxw), _ptr(wxb), _ptr(wow), _ptr(wob), _ptr(wq32),
+                   _ptr(wk32), ks, _ptr(wv32), _ptr(lam32), float(eps), _ptr(stats), _ptr(mom), _ptr(gate), _ptr(out), b, n,
+                   c, d, int(res), dt, st)
         else:
             _call("mrla_token_norm_pool", 0, _ptr(xc), _ptr(oc), _ptr(wxw), _ptr(wxb), float(eps), _ptr(stats), _ptr(mom), b, n,
                    c, dt, st)
@@ -1117,10 +1084,10 @@ class _TokenLightFn(torch.autograd.Function):
         sums = torch.empty((c * L.TOKEN_PARTIALS + 2 * ks,), dtype=torch.float32, device=dev)
         if _seq():
             try:
-                _seq_call("mrla_token_light_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(stats), _ptr(wxw), _ptr(wxb),
-                          _ptr(wow), _ptr(wob), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32), _ptr(gate), _ptr(lam32), _ptr(mom),
-                          _ptr(dxn), _ptr(part), prow, _ptr(bmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dx), _ptr(do), _ptr(sums),
-                          b, n, c, d, res, dt, st)
+                L.call("mrla_token_light_bwd", _ptr(dout), _ptr(xc), _ptr(oc), _ptr(stats), _ptr(wxw), _ptr(wxb),
+                       _ptr(wow), _ptr(wob), _ptr(wq32), _ptr(wk32), ks, _ptr(wv32), _ptr(gate), _ptr(lam32), _ptr(mom),
+                       _ptr(dxn), _ptr(part), prow, _ptr(bmom), _ptr(dyx), _ptr(dwqk_part), _ptr(dx), _ptr(do), _ptr(sums),
+                       b, n, c, d, res, dt, st)
             except L.MrlaHipError as e:
                 if getattr(e, "code", None) != L.EUNSUPPORTED:
                     raise
@@ -1261,8 +1228,96 @@ def mrla_token_base(x, lnx_w, lnx_b, wq, wk, wv, d, stage, eps=1e-6):
 # ======================================================================================================
 # fused BatchNorm2d (+ReLU)  -- the producer-side epilogue in front of the MRLA tail
 # ======================================================================================================
+class _BnActState:
+    """What the backward of relu?(BatchNorm2d(x)) needs beside its saved tensors (xc, gamma32, bnbuf); holds no tensor of the
+    graph (`box` is the _DeferredBnBox of a deferred BatchNorm, or None)."""
+    __slots__ = ("layout", "rows", "relu", "training", "gdtype", "box")
+
+    def __init__(self, layout, rows, relu, training, gdtype, box):
+        self.layout, self.rows, self.relu, self.training, self.gdtype, self.box = layout, rows, relu, training, gdtype, box
+
+
+def _bn_act_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer, pre_moments, box):
+    """y = relu?(BatchNorm2d(x)): one statistics pass + one elementwise pass.  Returns (outputs, tensors to save, state):
+    y, or -- deferred -- (x as the kernels read it, detached, and bnbuf)."""
+    _require_cuda(x, "fused bn/act forward")
+    layout, xc = _layout_of(x)
+    b, c, h, w = xc.shape
+    if layout == L.NHWC and c % (16 // xc.element_size()):
+        layout, xc = _layout_of(x, L.NCHW)           # the NHWC passes move 16-byte channel vectors
+    dt, dev, st = _DT[xc.dtype], xc.device, _stream()
+    mode = L.BN_TRAIN if training else L.BN_EVAL
+    bn = _BnForward(gamma, beta, running_mean, running_var, c, mode, momentum, eps, dev, "fused bn/act forward")
+    bnbuf = bn.bnbuf
+    rows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)           # partial-sum rows (b, or b*nsplit for NHWC)
+    frows, pivot = rows, None
+    records = training and pre_moments is not None
+    if records:                # the producer (the 1x1 convolution GEMM) already took them: pivoted records per row
+        amom, frows = pre_moments, pre_moments.shape[0]
+        if tuple(amom.shape) != (frows, c, L.GEMM_MOMENTS) or amom.dtype != torch.float32:
+            raise L.MrlaHipError("pre_moments must be float32 [rows, c, MRLA_GEMM_MOMENTS] records")
+    else:
+        amom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
+        if training:           # sums about a per-channel pivot (a sample of the channel): robust for |mean| >> sigma
+            pivot = torch.empty((c,), dtype=torch.float32, device=dev)
+    if defer and relu:
+        raise L.MrlaHipError("a deferred BatchNorm cannot carry a ReLU")
+    y = None if defer else torch.empty_like(xc)
+    if _seq():
+        L.call("mrla_bn_fwd", _ptr(xc), _ptr(amom) if records else None, frows, None if records else _ptr(amom), _ptr(pivot),
+               rows, _ptr(bn.gamma32), _ptr(bn.beta32), _ptr(bn.rs.rm), _ptr(bn.rs.rv), mode, bn.momentum, bn.eps, _ptr(bnbuf),
+               int(relu), _ptr(y), b, c, h, w, dt, layout, st)
+    else:
+        if records:
+            bn.stats_rows(amom, frows, c, st)
+        else:
+            if training:
+                _call("mrla_bn_plane_moments", xc.numel() * xc.element_size(), _ptr(xc), _ptr(amom), _ptr(pivot), b, c, h, w,
+                      dt, layout, st)
+            bn.stats(amom, pivot, frows, c, b * h * w // frows, st)
+        if y is not None:
+            _call("mrla_bn_act_fwd", xc.numel() * xc.element_size() * 2, _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]), int(relu),
+                  _ptr(y), b, c, h, w, dt, layout, st)
+    bn.finish()
+    state = _BnActState(layout, rows, int(relu), training, gamma.dtype, box if defer else None)
+    if state.box is not None:
+        state.box.center = bnbuf[2]
+    return ((xc.detach(), bnbuf) if defer else y), (xc, bn.gamma32, bnbuf), state
+
+
+def _bn_act_backward(saved, state, dy):
+    """(dx, dgamma, dbeta) of _bn_act_forward for the gradient `dy` of its (first) output."""
+    xc, gamma32, bnbuf = saved
+    b, c, h, w = xc.shape
+    dt, dev, st = _DT[xc.dtype], xc.device, _stream()
+    if dy.dtype != xc.dtype:
+        dy = dy.to(xc.dtype)
+    layout, rows = state.layout, state.rows
+    handed = state.box.take(dy) if state.box is not None else None      # (sum dz, sum dz*x) taken by the producer of dy
+    dy = _layout_of(dy, layout)[1]
+    es = xc.element_size()
+    if handed is not None:
+        tmom, rows = handed
+    else:
+        tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
+    kb = _BnBackward(c, dev)
+    dx = torch.empty_like(xc)
+    mode = L.BN_TRAIN if state.training else L.BN_EVAL
+    if _seq():
+        L.call("mrla_bn_bwd", _ptr(dy), _ptr(xc), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, int(handed is not None), mode,
+               state.relu, _ptr(kb.small), _ptr(dx), b, c, h, w, dt, layout, st)
+    else:
+        if handed is None:
+            _call("mrla_bn_plane_dmoments", xc.numel() * es * 2, _ptr(dy), _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
+                  _ptr(bnbuf[2]), state.relu, _ptr(tmom), b, c, h, w, dt, layout, st)
+        cb = kb.stats(tmom, gamma32, bnbuf, mode, 1, rows, c, b * h * w // rows, st)
+        _call("mrla_bn_act_bwd", xc.numel() * es * 3, _ptr(dy), _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(cb), state.relu,
+              _ptr(dx), b, c, h, w, dt, layout, st)
+    return (dx,) + kb.grads(state.gdtype)
+
+
 class _BnActFn(torch.autograd.Function):
-    """y = relu?(BatchNorm2d(x)): one statistics pass + one elementwise pass per direction.
+    """y = relu?(BatchNorm2d(x)): one statistics pass + one elementwise pass per direction (_bn_act_forward / _backward).
     defer: skip the forward elementwise pass; the result aliases x and (scale, shift) are returned beside it for the
     consumer (the fused MRLA producer) to apply.  The backward is the same either way."""
 
@@ -1270,94 +1325,20 @@ class _BnActFn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer=False,
                 pre_moments=None, box=None):
-        _require_cuda(x, "fused bn/act forward")
         ctx.set_materialize_grads(False)       # (no zero-filled gradient tensor for the non-differentiable second output)
-        layout, xc = _layout_of(x)
-        b, c, h, w = xc.shape
-        if layout == L.NHWC and c % (16 // xc.element_size()):
-            layout, xc = _layout_of(x, L.NCHW)           # the NHWC passes move 16-byte channel vectors
-        dt, dev, st = _DT[xc.dtype], xc.device, _stream()
-        gamma32, beta32 = _f32(gamma), _f32(beta)
-        rs = _RunningStats(running_mean, running_var, c, "fused bn/act forward")
-        bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
-        rows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)           # partial-sum rows (b, or b*nsplit for NHWC)
-        frows, pivot = rows, None
-        records = training and pre_moments is not None
-        if records:                # the producer (the 1x1 convolution GEMM) already took them: pivoted records per row
-            amom, frows = pre_moments, pre_moments.shape[0]
-            if tuple(amom.shape) != (frows, c, L.GEMM_MOMENTS) or amom.dtype != torch.float32:
-                raise L.MrlaHipError("pre_moments must be float32 [rows, c, MRLA_GEMM_MOMENTS] records")
-        else:
-            amom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-            if training:           # sums about a per-channel pivot (a sample of the channel): robust for |mean| >> sigma
-                pivot = torch.empty((c,), dtype=torch.float32, device=dev)
-        if defer and relu:
-            raise L.MrlaHipError("a deferred BatchNorm cannot carry a ReLU")
-        y = None if defer else torch.empty_like(xc)
-        if _seq():
-            _seq_call("mrla_bn_fwd", _ptr(xc), _ptr(amom) if records else None, frows, None if records else _ptr(amom),
-                      _ptr(pivot), rows, _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
-                      L.BN_TRAIN if training else L.BN_EVAL, float(momentum), float(eps), _ptr(bnbuf), int(relu), _ptr(y),
-                      b, c, h, w, dt, layout, st)
-        else:
-            if training and not records:
-                _call("mrla_bn_plane_moments", xc.numel() * xc.element_size(), _ptr(xc), _ptr(amom), _ptr(pivot), b, c, h, w,
-                      dt, layout, st)
-            if records:
-                _call("mrla_bn_stats_fwd_rows", 0, _ptr(amom), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv), L.BN_TRAIN,
-                       float(momentum), float(eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), frows, c, st)
-            else:
-                _call("mrla_bn_stats_fwd", 0, _ptr(amom), _ptr(pivot), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
-                       L.BN_TRAIN if training else L.BN_EVAL, float(momentum), float(eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
-                       _ptr(bnbuf[2]), _ptr(bnbuf[3]), frows, c, b * h * w // frows, st)
-            if y is not None:
-                _call("mrla_bn_act_fwd", xc.numel() * xc.element_size() * 2, _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]), int(relu),
-                      _ptr(y), b, c, h, w, dt, layout, st)
-        rs.finish(training)
-        ctx.training, ctx.relu, ctx.gdtype, ctx.layout, ctx.rows = training, int(relu), gamma.dtype, layout, rows
-        ctx.box = box if defer else None
-        if ctx.box is not None:
-            ctx.box.center = bnbuf[2]
-        ctx.save_for_backward(xc, gamma32, bnbuf)
+        out, saved, ctx.state = _bn_act_forward(x, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer,
+                                                pre_moments, box)
+        ctx.save_for_backward(*saved)
         if defer:
-            ctx.mark_non_differentiable(bnbuf)
-            return xc.detach(), bnbuf
-        return y
+            ctx.mark_non_differentiable(out[1])
+        return out
 
     @staticmethod
     @_on_device
     def backward(ctx, dy, _dbuf=None):
         if dy is None:
             return (None,) * 12
-        xc, gamma32, bnbuf = ctx.saved_tensors
-        b, c, h, w = xc.shape
-        dt, dev, st = _DT[xc.dtype], xc.device, _stream()
-        if dy.dtype != xc.dtype:
-            dy = dy.to(xc.dtype)
-        layout, rows = ctx.layout, ctx.rows
-        handed = ctx.box.take(dy) if ctx.box is not None else None      # (sum dz, sum dz*x) taken by the producer of dy
-        dy = _layout_of(dy, layout)[1]
-        es = xc.element_size()
-        if handed is not None:
-            tmom, rows = handed
-        else:
-            tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-        small = torch.empty((5, c), dtype=torch.float32, device=dev)          # cb[c,3] | dgamma | dbeta
-        dx = torch.empty_like(xc)
-        mode = L.BN_TRAIN if ctx.training else L.BN_EVAL
-        if _seq():
-            _seq_call("mrla_bn_bwd", _ptr(dy), _ptr(xc), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, int(handed is not None),
-                      mode, ctx.relu, _ptr(small), _ptr(dx), b, c, h, w, dt, layout, st)
-        else:
-            if handed is None:
-                _call("mrla_bn_plane_dmoments", xc.numel() * es * 2, _ptr(dy), _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
-                      _ptr(bnbuf[2]), ctx.relu, _ptr(tmom), b, c, h, w, dt, layout, st)
-            cb = small[:3].view(c, 3)
-            _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), mode, 1, _ptr(cb),
-                  _ptr(small[3]), _ptr(small[4]), rows, c, b * h * w // rows, st)
-            _call("mrla_bn_act_bwd", xc.numel() * es * 3, _ptr(dy), _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(cb), ctx.relu,
-                  _ptr(dx), b, c, h, w, dt, layout, st)
-        return dx, small[3].to(ctx.gdtype), small[4].to(ctx.gdtype), None, None, None, None, None, None, None, None, None
+        return _bn_act_backward(ctx.saved_tensors, ctx.state, dy) + (None,) * 9
 
 
 def bn_act(x, bn, relu, defer=False, pre_moments=None):
@@ -1365,18 +1346,17 @@ def bn_act(x, bn, relu, defer=False, pre_moments=None):
     device the kernels do not handle) runs as the caller's module followed by torch.relu.
     defer=True (relu must be False): only the statistics are taken; the returned tensor aliases x and carries the
     per-channel affine as `._mrla_affine` for `mrla_light(..., pre_activation=True)` to apply in its first pass."""
-    if (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats and x.is_cuda and x.dim() == 4
+    if (_is_fused_bn(bn) and x.is_cuda and x.dim() == 4
             and x.dtype in _DT and (x.is_contiguous() or x.is_contiguous(memory_format=_CL))):
-        training = bn.training
-        momentum = bump_batch_counter(bn) if training else bn.momentum
+        training, momentum = _bn_step(bn)
         if defer:
             box = _DeferredBnBox()
-            y, buf = _BnActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0,
+            y, buf = _BnActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum,
                                     bn.eps, False, True, pre_moments, box)
             y._mrla_affine = (buf[0], buf[1])
             y._mrla_bn_box = box
             return y
-        return _BnActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0, bn.eps,
+        return _BnActFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps,
                               relu, False, pre_moments)
     y = bn(x)
     return torch.relu(y) if relu else y
@@ -1399,10 +1379,10 @@ class _BnGateFn(torch.autograd.Function):
         hw = h * w
         dt, dev, st = _DT[y.dtype], y.device, _stream()
         lay = L.NHWC
-        gamma32, beta32 = _f32(gamma), _f32(beta)
-        rs = _RunningStats(running_mean, running_var, c, "bn + channel gate forward")
+        bn = _BnForward(gamma, beta, running_mean, running_var, c, L.BN_TRAIN if training else L.BN_EVAL, momentum, eps, dev,
+                        "bn + channel gate forward")
+        bnbuf = bn.bnbuf
         f32 = dict(dtype=torch.float32, device=dev)
-        bnbuf = torch.empty((4, c), **f32)                                   # sc, sh, save_mean, save_inv
         rows = L.load().mrla_bn_moment_rows(b, c, h, w, lay)
         amom = torch.empty((rows, c, 2), **f32)
         pivot = torch.empty((c,), **f32) if training else None
@@ -1410,9 +1390,7 @@ class _BnGateFn(torch.autograd.Function):
         es = y.element_size()
         # the plane sums are wanted in eval mode too: they are the pool
         _call("mrla_bn_plane_moments", y.numel() * es, _ptr(y), _ptr(amom), _ptr(pivot), b, c, h, w, dt, lay, st)
-        _call("mrla_bn_stats_fwd", 0, _ptr(amom), _ptr(pivot), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
-              L.BN_TRAIN if training else L.BN_EVAL, float(momentum), float(eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
-              _ptr(bnbuf[2]), _ptr(bnbuf[3]), rows, c, b * hw // rows, st)
+        bn.stats(amom, pivot, rows, c, b * hw // rows, st)
         _call("mrla_bn_gate_pool", 0, _ptr(amom), _ptr(pivot), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(sp[0]), _ptr(sp[1]),
               b, c, h, w, lay, st)
         hid = None
@@ -1430,10 +1408,10 @@ class _BnGateFn(torch.autograd.Function):
         out = torch.empty_like(y)
         _call("mrla_bn_gate_fwd", y.numel() * es * 2, _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(g), _ptr(out), b, c, h, w,
               dt, lay, st)
-        rs.finish(training)
+        bn.finish()
         ctx.training, ctx.kind, ctx.rows = training, kind, rows
         ctx.gdtype, ctx.wmeta = gamma.dtype, [(t.dtype, tuple(t.shape)) for t in weights]
-        ctx.save_for_backward(y, gamma32, bnbuf, sp, g, *saved_w)
+        ctx.save_for_backward(y, bn.gamma32, bnbuf, sp, g, *saved_w)
         return out
 
     @staticmethod
@@ -1454,7 +1432,7 @@ class _BnGateFn(torch.autograd.Function):
         arows = torch.empty((ctx.rows, c, 2), **f32)
         dg = torch.empty((b, c), **f32)
         tmom = torch.empty((b, c, 2), **f32)
-        small = torch.empty((5, c), **f32)                                   # cb[c,3] | dgamma | dbeta
+        kb = _BnBackward(c, dev)
         sums = (_ptr(arows), _ptr(sp[0]), _ptr(g))
         bn3 = (_ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]))
         _call("mrla_bn_plane_dmoments", y.numel() * es * 2, _ptr(do), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), 0,
@@ -1478,14 +1456,12 @@ class _BnGateFn(torch.autograd.Function):
                 q = torch.mm(dh, w1).div_(float(hw))
             wgrads = (dw1, dw2)
         _call("mrla_bn_gate_sums_bwd", 0, *sums, _ptr(q), *bn3, None, _ptr(tmom), b, c, h, w, lay, st)
-        cb = small[:3].view(c, 3)
-        _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]),
-              L.BN_TRAIN if ctx.training else L.BN_EVAL, 1, _ptr(cb), _ptr(small[3]), _ptr(small[4]), b, c, hw, st)
+        cb = kb.stats(tmom, gamma32, bnbuf, L.BN_TRAIN if ctx.training else L.BN_EVAL, 1, b, c, hw, st)
         dy = torch.empty_like(y)
         _call("mrla_bn_gate_bwd", y.numel() * es * 3, _ptr(do), _ptr(y), _ptr(cb), _ptr(g), _ptr(q), _ptr(dy), b, c, h, w, dt,
               lay, st)
         wg = tuple(t.reshape(shape).to(dtype) for t, (dtype, shape) in zip(wgrads, ctx.wmeta))
-        return (dy, small[3].to(ctx.gdtype), small[4].to(ctx.gdtype), None, None, None, None, None, None) + wg
+        return (dy,) + kb.grads(ctx.gdtype) + (None,) * 6 + wg
 
 
 def bn_gate_applies(shape, dtype, channels_last, is_cuda, bn, se=None, eca=None):
@@ -1494,7 +1470,7 @@ def bn_gate_applies(shape, dtype, channels_last, is_cuda, bn, se=None, eca=None)
     and y is a channels_last CUDA tensor of a shape mrla_bn_gate_supported takes."""
     if not (CHANNEL_GATE and TIMER is None and (se is None) != (eca is None)):
         return False
-    if not (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats):
+    if not _is_fused_bn(bn):
         return False
     if not (is_cuda and len(shape) == 4 and dtype in _DT and channels_last):
         return False
@@ -1512,13 +1488,12 @@ def bn_gate(x, bn, se=None, eca=None, pre_moments=None):
     are its pool as well)."""
     if x.dim() == 4 and bn_gate_applies(tuple(x.shape), x.dtype, x.is_contiguous(memory_format=_CL), x.is_cuda, bn, se, eca) \
             and x.data_ptr() % 16 == 0:
-        training = bn.training
-        momentum = bump_batch_counter(bn) if training else bn.momentum
+        training, momentum = _bn_step(bn)
         if eca is not None:
             kind, weights = 0, (eca.conv.weight,)
         else:
             kind, weights = 1, (se.fc[0].weight, se.fc[2].weight)
-        return _BnGateFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0, bn.eps,
+        return _BnGateFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps,
                                kind, *weights)
     out = bn_act(x, bn, False, pre_moments=pre_moments)
     if se is not None:
@@ -1540,30 +1515,27 @@ class _BnReluPoolFn(torch.autograd.Function):
         layout, xc = _layout_of(x, L.NHWC)
         b, c, h, w = xc.shape
         dt, dev, st = _DT[xc.dtype], xc.device, _stream()
-        gamma32, beta32 = _f32(gamma), _f32(beta)
-        rs = _RunningStats(running_mean, running_var, c, "fused bn/relu/maxpool forward")
-        bnbuf = torch.empty((4, c), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
+        mode = L.BN_TRAIN if training else L.BN_EVAL
+        bn = _BnForward(gamma, beta, running_mean, running_var, c, mode, momentum, eps, dev, "fused bn/relu/maxpool forward")
+        bnbuf = bn.bnbuf
         rows = L.load().mrla_bn_moment_rows(b, c, h, w, layout)
         amom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
         pivot = torch.empty((c,), dtype=torch.float32, device=dev) if training else None
         ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         out = torch.empty((b, c, ho, wo), dtype=xc.dtype, device=dev, memory_format=_CL)
-        mode = L.BN_TRAIN if training else L.BN_EVAL
         if _seq():
-            _seq_call("mrla_stem_fwd", _ptr(xc), _ptr(amom), _ptr(pivot), rows, _ptr(gamma32), _ptr(beta32), _ptr(rs.rm),
-                      _ptr(rs.rv), mode, float(momentum), float(eps), _ptr(bnbuf), _ptr(out), b, c, h, w, dt, layout, st)
+            L.call("mrla_stem_fwd", _ptr(xc), _ptr(amom), _ptr(pivot), rows, _ptr(bn.gamma32), _ptr(bn.beta32), _ptr(bn.rs.rm),
+                   _ptr(bn.rs.rv), mode, bn.momentum, bn.eps, _ptr(bnbuf), _ptr(out), b, c, h, w, dt, layout, st)
         else:
             if training:
                 _call("mrla_bn_plane_moments", xc.numel() * xc.element_size(), _ptr(xc), _ptr(amom), _ptr(pivot), b, c, h, w, dt,
                       layout, st)
-            _call("mrla_bn_stats_fwd", 0, _ptr(amom), _ptr(pivot), _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv),
-                   mode, float(momentum), float(eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), rows, c,
-                   b * h * w // rows, st)
+            bn.stats(amom, pivot, rows, c, b * h * w // rows, st)
             _call("mrla_bn_relu_pool_fwd", (xc.numel() + out.numel()) * xc.element_size(), _ptr(xc), _ptr(bnbuf[0]),
                   _ptr(bnbuf[1]), _ptr(out), b, c, h, w, dt, layout, st)
-        rs.finish(training)
+        bn.finish()
         ctx.training, ctx.gdtype = training, gamma.dtype
-        ctx.save_for_backward(xc, gamma32, bnbuf)
+        ctx.save_for_backward(xc, bn.gamma32, bnbuf)
         return out
 
     @staticmethod
@@ -1579,22 +1551,20 @@ class _BnReluPoolFn(torch.autograd.Function):
         rows = L.load().mrla_bn_pool_rows(b, c, h, w, dt, L.NHWC)
         L.check(min(rows, 0), "mrla_bn_pool_rows")
         tmom = torch.empty((rows, c, 2), dtype=torch.float32, device=dev)
-        small = torch.empty((5, c), dtype=torch.float32, device=dev)          # cb[c,3] | dgamma | dbeta
+        kb = _BnBackward(c, dev)
         dx = torch.empty_like(xc) if ctx.needs_input_grad[0] else None
         mode = L.BN_TRAIN if ctx.training else L.BN_EVAL
         if _seq():
-            _seq_call("mrla_stem_bwd", _ptr(dp), _ptr(xc), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, mode, _ptr(small),
-                      _ptr(dx), b, c, h, w, dt, L.NHWC, st)
+            L.call("mrla_stem_bwd", _ptr(dp), _ptr(xc), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, mode, _ptr(kb.small),
+                   _ptr(dx), b, c, h, w, dt, L.NHWC, st)
         else:
             _call("mrla_bn_relu_pool_dmoments", (xc.numel() + dp.numel()) * es, _ptr(dp), _ptr(xc), _ptr(bnbuf[0]), _ptr(bnbuf[1]),
                   _ptr(bnbuf[2]), _ptr(tmom), b, c, h, w, dt, L.NHWC, st)
-            cb = small[:3].view(c, 3)
-            _call("mrla_bn_stats_bwd", 0, _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), mode, 1, _ptr(cb),
-                  _ptr(small[3]), _ptr(small[4]), rows, c, b * h * w // rows, st)
+            cb = kb.stats(tmom, gamma32, bnbuf, mode, 1, rows, c, b * h * w // rows, st)
             if dx is not None:
                 _call("mrla_bn_relu_pool_bwd", (2 * xc.numel() + dp.numel()) * es, _ptr(dp), _ptr(xc), _ptr(bnbuf[0]),
                       _ptr(bnbuf[1]), _ptr(cb), _ptr(dx), b, c, h, w, dt, L.NHWC, st)
-        return dx, small[3].to(ctx.gdtype), small[4].to(ctx.gdtype), None, None, None, None, None
+        return (dx,) + kb.grads(ctx.gdtype) + (None,) * 5
 
 
 def bn_relu_maxpool(x, bn, pool):
@@ -1603,15 +1573,14 @@ def bn_relu_maxpool(x, bn, pool):
     any other configuration runs `pool(bn_act(x, bn, relu=True))`."""
     def _pair(v):
         return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-    if (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats and type(pool) is torch.nn.MaxPool2d
+    if (_is_fused_bn(bn) and type(pool) is torch.nn.MaxPool2d
             and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2) and _pair(pool.padding) == (1, 1)
             and _pair(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices
             and x.is_cuda and x.dim() == 4 and x.dtype in _DT and x.is_contiguous(memory_format=_CL)
             and x.data_ptr() % 16 == 0
             and L.load().mrla_bn_pool_rows(x.shape[0], x.shape[1], x.shape[2], x.shape[3], _DT[x.dtype], L.NHWC) > 0):
-        training = bn.training
-        momentum = bump_batch_counter(bn) if training else bn.momentum
-        return _BnReluPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0, bn.eps)
+        training, momentum = _bn_step(bn)
+        return _BnReluPoolFn.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum, bn.eps)
     return pool(bn_act(x, bn, relu=True))
 
 
@@ -1705,6 +1674,143 @@ class WeightBank:
         return self.entries.get(id(conv)) if dtype == self.dtype else None
 
 
+class _GemmState:
+    """What the backward of the 1x1 GEMM convolution needs beside its saved tensors (x, w, w16t); holds no tensor."""
+    __slots__ = ("sub", "wshape", "wstride", "wdtype", "f32")
+
+    def __init__(self, sub, wshape, wstride, wdtype, f32):
+        self.sub, self.wshape, self.wstride, self.wdtype, self.f32 = sub, wshape, wstride, wdtype, f32
+
+
+def _conv1x1_forward(x, w, want_moments, passthrough, w16, w16t, sub):
+    """The forward of _Conv1x1Fn (its docstrings describe the arguments).  Returns (outputs, tensors to save, state):
+    outputs = (y, moment records or an empty tensor[, x or its subsample])."""
+    sub = tuple(sub) if (passthrough and sub is not None) else None
+    b, k, h, wd = x.shape
+    n = w.shape[0]
+    m = b * h * wd
+    dev, st = x.device, _stream()
+    wshape, wstride, wdtype = w.shape, w.stride(), w.dtype   # [n, k] or the module's [n, k, 1, 1]
+    if w16 is not None:
+        w = w16
+    else:
+        w = w.reshape(n, k)                            # (a view: the 1x1 taps carry no data)
+        if not w.is_contiguous():
+            w = w.contiguous()
+    part = None
+    # fp32 operands (CONV1X1_F32): the GEMMs of conv1x1_f32.hip; remembered for the backward, whatever the switch says then
+    f32 = (CONV1X1_F32 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.data_ptr() % 16 == 0
+           and w.data_ptr() % 16 == 0)
+    rows = (L.load().mrla_conv1x1_f32_rows(m, k, n) if f32
+            else L.load().mrla_conv1x1_rows(m, k, n, _DT[x.dtype]))   # > 0: supported, that many moment-record rows; < 0: not taken
+    if f32 and rows > 0:
+        y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
+        if want_moments:
+            part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
+        _call("mrla_conv1x1_f32_fwd", (x.numel() + y.numel()) * 4, _ptr(x), _ptr(w), 0, _ptr(y), _ptr(part), m, k, n, st)
+    elif rows >= 0:
+        y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
+        if want_moments and rows > 0:
+            part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
+        _call("mrla_conv1x1_fwd", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w), _ptr(y), _ptr(part), m, k,
+              n, _DT[x.dtype], st)
+    else:
+        y = torch.nn.functional.conv2d(x, w.view(n, k, 1, 1))
+    if part is None:
+        part = torch.empty(0, device=dev)
+    outs = (y, part)
+    if sub is not None:
+        outs += (x[:, :, ::sub[0], ::sub[1]].contiguous(memory_format=_CL),)
+    elif passthrough:           # x itself as a third output: its gradient (the shortcut's) comes back to the backward
+        outs += (x,)
+    return outs, (x, w, w16t), _GemmState(sub, wshape, wstride, wdtype, f32)
+
+
+def _conv1x1_backward(saved, state, needs, dy, d_through):
+    """(gx, gw) of _conv1x1_forward.  needs: (the input, the weight) want their gradient; dy: the gradient of y, None when
+    only the shortcut carried one; d_through: the gradient of the third output, or None."""
+    x, w, w16t = saved
+    sub = state.sub
+    sh, sw = sub if sub is not None else (1, 1)
+    if dy is None:             # only the shortcut carried a gradient
+        if d_through is not None and sub is not None:
+            d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
+        return (d_through if needs[0] else None), None
+    dy = dy.contiguous(memory_format=_CL)
+    n, k = w.shape
+    b, _, h, wd = x.shape
+    m = b * h * wd
+    lib, dt = L.load(), _DT[x.dtype]
+    need_x, need_w = needs
+    gx = gw = None
+    same = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
+    # the input gradient is the same GEMM with the transposed weight: dX[m, k] = sum_n dY[m, n] * W^T[k, n]
+    # (no memset of dX, as MIOpen's backward-data solver needs); shapes the kernel does not take stay on MIOpen
+    if d_through is not None and (d_through.dtype != x.dtype or not d_through.is_contiguous(memory_format=_CL)
+                                  or d_through.data_ptr() % 16):
+        d_through = d_through.to(x.dtype).contiguous(memory_format=_CL)
+    if state.f32:
+        # fp32: dX on the weight as stored ([n, k] is reduction-major for this product: w_trans = 1, no transposed copy),
+        # dW straight into an fp32 [n, k]; the shortcut's gradient is added by the tail below
+        if need_x and same and lib.mrla_conv1x1_f32_rows(m, n, k) > 0:
+            gx = torch.empty_like(x)
+            _call("mrla_conv1x1_f32_bwd_data", (dy.numel() + gx.numel()) * 4, _ptr(dy), _ptr(w), 1, _ptr(gx), None, m, n, k,
+                  _stream(), entry="mrla_conv1x1_f32_fwd")
+            need_x = False
+        rows = lib.mrla_conv1x1_f32_wgrad_rows(m, k, n) if (need_w and same) else 0
+        if rows > 0:
+            part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
+            gw = torch.empty((n, k), dtype=torch.float32, device=x.device)
+            _call("mrla_conv1x1_f32_wgrad", (dy.numel() + x.numel()) * 4, _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), m, k, n,
+                  _stream())
+            need_w = False
+    elif need_x and same and lib.mrla_conv1x1_rows(m, n, k, dt) >= 0:
+        gx = torch.empty_like(x)
+        wt = w16t if w16t is not None else w.t().contiguous()
+        if d_through is not None and SHORTCUT_ADDEND and lib.mrla_conv1x1_addend_supported(m, n, k, sh, sw, dt) == 1:
+            # ... + the shortcut's gradient inside the GEMM, whichever kernel form takes the shape, and from the compact
+            # gradient of a strided block's subsample as it is (no zero-fill, no scatter, a quarter of the addend bytes)
+            _call("mrla_conv1x1_bwd_data", (dy.numel() + gx.numel() + d_through.numel()) * x.element_size(), _ptr(dy),
+                  _ptr(wt), _ptr(d_through), _ptr(gx), m, n, k, b, h, wd, sh, sw, dt, _stream(),
+                  entry="mrla_conv1x1_fwd_addend")
+            d_through = None
+        elif d_through is not None and lib.mrla_conv1x1_add_supported(m, n, k, dt) == 1:
+            # ... + the shortcut's gradient in the wide GEMM's epilogue (fp32 sum, one rounding) instead of a separate
+            # accumulation pass over the block input's gradient
+            if sub is not None:
+                d_through, sub = _scatter_subsample(d_through, x.shape, sh, sw, _CL), None
+            _call("mrla_conv1x1_bwd_data", (dy.numel() + 2 * gx.numel()) * x.element_size(), _ptr(dy), _ptr(wt),
+                  _ptr(d_through), _ptr(gx), m, n, k, dt, _stream(), entry="mrla_conv1x1_fwd_add")
+            d_through = None
+        else:
+            _call("mrla_conv1x1_bwd_data", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wt), _ptr(gx),
+                  None, m, n, k, dt, _stream(), entry="mrla_conv1x1_fwd")
+        need_x = False
+    # the weight gradient dW[n, k] = sum_m dY[m, n] * X[m, k]: one pass over both activations, per-workgroup partial
+    # tiles summed by a second kernel (MIOpen: memset + atomics into fp32 + a cast kernel)
+    if need_w and same and not state.f32 and w.dtype == x.dtype and state.wdtype in (x.dtype, torch.float32):
+        rows = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
+        if rows > 0:
+            part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
+            gw = torch.empty((n, k), dtype=state.wdtype, device=x.device)       # the master's dtype, no cast kernel behind
+            _call("mrla_conv1x1_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part),
+                  _ptr(gw), m, k, n, dt, _DT[state.wdtype], _stream())
+            need_w = False
+    if need_x or need_w:
+        gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w.view(n, k, 1, 1), None, (1, 1), (0, 0), (1, 1), False,
+                                                          (0, 0), 1, [need_x, need_w, False])
+        gx = gx2 if need_x else gx
+        gw = gw2.reshape(n, k) if need_w else gw
+    if d_through is not None and needs[0]:
+        # what no GEMM took: a shape or dtype off the HIP path, SHORTCUT_ADDEND off and a form other than the wide one
+        if sub is not None:
+            d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
+        gx = gx + d_through
+    if gw is not None:          # the weight's own dtype, shape AND strides (autograd's / DDP's gradient layout contract)
+        gw = _grad_like(gw.to(state.wdtype), state.wshape, state.wstride)
+    return gx, gw
+
+
 class _Conv1x1Fn(torch.autograd.Function):
     """y = conv2d(x, w) for a bias-free 1x1 stride-1 convolution of a channels_last bf16 or fp16 tensor (fp32 under CONV1X1_F32: the GEMMs of
     conv1x1_f32.hip, mrla_conv1x1_f32_fwd / _wgrad, the same roles), plus the partial
@@ -1716,139 +1822,28 @@ class _Conv1x1Fn(torch.autograd.Function):
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, want_moments, passthrough=False, w16=None, w16t=None, sub=None):
+    def forward(ctx, x, w, want_moments, passthrough=False, w16=None, w16t=None, sub=None, keep=None):
         """w16 / w16t: working copies [n, k] / [k, n], of x's dtype, of an fp32 master weight `w` (WeightBank); the weight gradient
         is then returned in the master's dtype straight from the reduction kernel.
         sub = (sh, sw), with passthrough: the third output is x[:, :, ::sh, ::sw] (dense channels_last) instead of x -- the
         input of the block's strided downsample convolution.  Its gradient then comes back COMPACT, and the input-gradient
         GEMM reads it in place (mrla_conv1x1_fwd_addend) instead of a zero-filled full-size tensor it was scattered into.
         It is an ordinary output of this node: a second consumer, a hook or torch.autograd.grad on it see the true
-        gradient of the subsampled tensor, whichever path the backward then takes."""
+        gradient of the subsampled tensor, whichever path the backward then takes.
+        keep: a list that receives (tensors saved, state) -- for _ConvBnFn, which runs this forward as the first half of
+        its own and keeps both on its own context."""
         ctx.set_materialize_grads(False)       # (the moment rows carry no gradient; the shortcut's may be absent)
-        ctx.sub = tuple(sub) if (passthrough and sub is not None) else None
-        b, k, h, wd = x.shape
-        n = w.shape[0]
-        m = b * h * wd
-        dev, st = x.device, _stream()
-        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype   # [n, k] or the module's [n, k, 1, 1]
-        if w16 is not None:
-            w = w16
-        else:
-            w = w.reshape(n, k)                            # (a view: the 1x1 taps carry no data)
-            if not w.is_contiguous():
-                w = w.contiguous()
-        part = None
-        # fp32 operands (CONV1X1_F32): the GEMMs of conv1x1_f32.hip; remembered for the backward, whatever the switch says then
-        ctx.f32 = (CONV1X1_F32 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.data_ptr() % 16 == 0
-                   and w.data_ptr() % 16 == 0)
-        rows = (L.load().mrla_conv1x1_f32_rows(m, k, n) if ctx.f32
-                else L.load().mrla_conv1x1_rows(m, k, n, _DT[x.dtype]))   # > 0: supported, that many moment-record rows; < 0: not taken
-        if ctx.f32 and rows > 0:
-            y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
-            if want_moments:
-                part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
-            _call("mrla_conv1x1_f32_fwd", (x.numel() + y.numel()) * 4, _ptr(x), _ptr(w), 0, _ptr(y), _ptr(part), m, k, n, st)
-        elif rows >= 0:
-            y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
-            if want_moments and rows > 0:
-                part = torch.empty((rows, n, L.GEMM_MOMENTS), dtype=torch.float32, device=dev)
-            _call("mrla_conv1x1_fwd", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w), _ptr(y), _ptr(part), m, k,
-                  n, _DT[x.dtype], st)
-        else:
-            y = torch.nn.functional.conv2d(x, w.view(n, k, 1, 1))
-        ctx.save_for_backward(x, w, w16t)
-        if part is None:
-            part = torch.empty(0, device=dev)
-        ctx.mark_non_differentiable(part)
-        if ctx.sub is not None:
-            return y, part, x[:, :, ::ctx.sub[0], ::ctx.sub[1]].contiguous(memory_format=_CL)
-        if passthrough:             # x itself as a third output: its gradient (the shortcut's) comes back to backward()
-            return y, part, x
-        return y, part
+        outs, saved, ctx.state = _conv1x1_forward(x, w, want_moments, passthrough, w16, w16t, sub)
+        ctx.save_for_backward(*saved)
+        ctx.mark_non_differentiable(outs[1])
+        if keep is not None:
+            keep += (saved, ctx.state)
+        return outs
 
     @staticmethod
     @_on_device
     def backward(ctx, dy, _dpart=None, d_through=None):
-        x, w, w16t = ctx.saved_tensors
-        sub = ctx.sub
-        sh, sw = sub if sub is not None else (1, 1)
-        if dy is None:             # only the shortcut carried a gradient
-            if d_through is not None and sub is not None:
-                d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
-            return (d_through if ctx.needs_input_grad[0] else None), None, None, None, None, None, None
-        dy = dy.contiguous(memory_format=_CL)
-        n, k = w.shape
-        b, _, h, wd = x.shape
-        m = b * h * wd
-        lib, dt = L.load(), _DT[x.dtype]
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx = gw = None
-        same = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
-        # the input gradient is the same GEMM with the transposed weight: dX[m, k] = sum_n dY[m, n] * W^T[k, n]
-        # (no memset of dX, as MIOpen's backward-data solver needs); shapes the kernel does not take stay on MIOpen
-        if d_through is not None and (d_through.dtype != x.dtype or not d_through.is_contiguous(memory_format=_CL)
-                                      or d_through.data_ptr() % 16):
-            d_through = d_through.to(x.dtype).contiguous(memory_format=_CL)
-        if ctx.f32:
-            # fp32: dX on the weight as stored ([n, k] is reduction-major for this product: w_trans = 1, no transposed copy),
-            # dW straight into an fp32 [n, k]; the shortcut's gradient is added by the tail below
-            if need_x and same and lib.mrla_conv1x1_f32_rows(m, n, k) > 0:
-                gx = torch.empty_like(x)
-                _call("mrla_conv1x1_f32_bwd_data", (dy.numel() + gx.numel()) * 4, _ptr(dy), _ptr(w), 1, _ptr(gx), None, m, n, k,
-                      _stream(), entry="mrla_conv1x1_f32_fwd")
-                need_x = False
-            rows = lib.mrla_conv1x1_f32_wgrad_rows(m, k, n) if (need_w and same) else 0
-            if rows > 0:
-                part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
-                gw = torch.empty((n, k), dtype=torch.float32, device=x.device)
-                _call("mrla_conv1x1_f32_wgrad", (dy.numel() + x.numel()) * 4, _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), m, k, n,
-                      _stream())
-                need_w = False
-        elif need_x and same and lib.mrla_conv1x1_rows(m, n, k, dt) >= 0:
-            gx = torch.empty_like(x)
-            wt = w16t if w16t is not None else w.t().contiguous()
-            if d_through is not None and SHORTCUT_ADDEND and lib.mrla_conv1x1_addend_supported(m, n, k, sh, sw, dt) == 1:
-                # ... + the shortcut's gradient inside the GEMM, whichever kernel form takes the shape, and from the compact
-                # gradient of a strided block's subsample as it is (no zero-fill, no scatter, a quarter of the addend bytes)
-                _call("mrla_conv1x1_bwd_data", (dy.numel() + gx.numel() + d_through.numel()) * x.element_size(), _ptr(dy),
-                      _ptr(wt), _ptr(d_through), _ptr(gx), m, n, k, b, h, wd, sh, sw, dt, _stream(),
-                      entry="mrla_conv1x1_fwd_addend")
-                d_through = None
-            elif d_through is not None and lib.mrla_conv1x1_add_supported(m, n, k, dt) == 1:
-                # ... + the shortcut's gradient in the wide GEMM's epilogue (fp32 sum, one rounding) instead of a separate
-                # accumulation pass over the block input's gradient
-                if sub is not None:
-                    d_through, sub = _scatter_subsample(d_through, x.shape, sh, sw, _CL), None
-                _call("mrla_conv1x1_bwd_data", (dy.numel() + 2 * gx.numel()) * x.element_size(), _ptr(dy), _ptr(wt),
-                      _ptr(d_through), _ptr(gx), m, n, k, dt, _stream(), entry="mrla_conv1x1_fwd_add")
-                d_through = None
-            else:
-                _call("mrla_conv1x1_bwd_data", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wt), _ptr(gx),
-                      None, m, n, k, dt, _stream(), entry="mrla_conv1x1_fwd")
-            need_x = False
-        # the weight gradient dW[n, k] = sum_m dY[m, n] * X[m, k]: one pass over both activations, per-workgroup partial
-        # tiles summed by a second kernel (MIOpen: memset + atomics into fp32 + a cast kernel)
-        if need_w and same and not ctx.f32 and w.dtype == x.dtype and ctx.wdtype in (x.dtype, torch.float32):
-            rows = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
-            if rows > 0:
-                part = torch.empty((rows, n, k), dtype=torch.float32, device=x.device)
-                gw = torch.empty((n, k), dtype=ctx.wdtype, device=x.device)       # the master's dtype, no cast kernel behind
-                _call("mrla_conv1x1_wgrad", (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part),
-                      _ptr(gw), m, k, n, dt, _DT[ctx.wdtype], _stream())
-                need_w = False
-        if need_x or need_w:
-            gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w.view(n, k, 1, 1), None, (1, 1), (0, 0), (1, 1), False,
-                                                              (0, 0), 1, [need_x, need_w, False])
-            gx = gx2 if need_x else gx
-            gw = gw2.reshape(n, k) if need_w else gw
-        if d_through is not None and ctx.needs_input_grad[0]:
-            # what no GEMM took: a shape or dtype off the HIP path, SHORTCUT_ADDEND off and a form other than the wide one
-            if sub is not None:
-                d_through = _scatter_subsample(d_through, x.shape, sh, sw, _CL)
-            gx = gx + d_through
-        if gw is not None:          # the weight's own dtype, shape AND strides (autograd's / DDP's gradient layout contract)
-            gw = _grad_like(gw.to(ctx.wdtype), ctx.wshape, ctx.wstride)
-        return gx, gw, None, None, None, None, None
+        return _conv1x1_backward(ctx.saved_tensors, ctx.state, ctx.needs_input_grad[:2], dy, d_through) + (None,) * 6
 
 
 def _scatter_subsample(g, shape, sh, sw, fmt):
@@ -1876,31 +1871,14 @@ class _SubsampleFn(torch.autograd.Function):
         return _scatter_subsample(g, ctx.shape, ctx.s[0], ctx.s[1], ctx.fmt), None, None
 
 
-class _SubCtx:
-    """What _Conv1x1Fn / _BnActFn ask of their autograd context, for _ConvBnFn to run their bodies as its two halves: the
-    tensors they save go into the real node's save_for_backward, everything else is plain attributes."""
-
-    def __init__(self):
-        self.saved_tensors, self.needs_input_grad = (), ()
-        self.f32 = False            # (_ConvBnFn is a 16-bit node: never the fp32 GEMMs of _Conv1x1Fn)
-
-    def set_materialize_grads(self, flag):
-        pass
-
-    def save_for_backward(self, *tensors):
-        self.saved_tensors = tensors
-
-    def mark_non_differentiable(self, *tensors):
-        pass
-
-
 class _ConvBnFn(torch.autograd.Function):
     """relu?(BatchNorm2d(conv1x1(x))) as ONE autograd node, so that its backward can hand the gradient arriving at the
     BatchNorm's output straight to the weight-gradient GEMM (mrla_conv1x1_wgrad_bn): the BatchNorm backward apply pass
     dy = e*dz + f*y + h is formed inside that GEMM, which writes dy once for the input-gradient GEMM -- the tensor between
-    the two halves never leaves this node.  The forward IS _Conv1x1Fn.forward followed by _BnActFn.forward, the backward is
-    theirs wherever the fused kernel does not apply (frozen weight, a gradient of another dtype or layout, an active
-    KernelTimer, WGRAD_BN off): same kernels, same order, same values.
+    the two halves never leaves this node.  The forward IS _Conv1x1Fn's followed by _bn_act_forward, the backward is
+    _bn_act_backward and _conv1x1_backward wherever the fused kernel does not apply (frozen weight, a gradient of another
+    dtype or layout, an active KernelTimer, WGRAD_BN off): same kernels, same order, same values.  The node keeps the two
+    halves' states (_GemmState, _BnActState: no tensors) and one list of saved tensors.
     Outputs: (out[, x']) or, deferred, (y, bnbuf[, x']) -- y the raw convolution output, bnbuf not differentiable; x' the
     passthrough / subsample output of _Conv1x1Fn."""
 
@@ -1910,21 +1888,17 @@ class _ConvBnFn(torch.autograd.Function):
                 w16, w16t, sub, fuse_dx=False):
         ctx.set_materialize_grads(False)
         ctx.fuse_dx = bool(fuse_dx)
-        ca, cb = _SubCtx(), _SubCtx()
         # (gradients are off inside a forward: this call adds no node, it is _Conv1x1Fn's forward and nothing else.  Through
-        # .apply, not .forward(ca, ...): _Conv1x1Fn.apply is where the GEMM route is observed from outside, for this node too;
-        # the price is that ca is filled here with what _Conv1x1Fn.forward keeps for its backward)
-        res = _Conv1x1Fn.apply(x, w, bool(training), passthrough, w16, w16t, sub)
-        n, k = w.shape[0], x.shape[1]
-        ca.sub = tuple(sub) if (passthrough and sub is not None) else None
-        ca.wshape, ca.wstride, ca.wdtype = w.shape, w.stride(), w.dtype
-        ca.saved_tensors = (x, w16 if w16 is not None else w.reshape(n, k).contiguous(), w16t)
+        # .apply, not the body itself: _Conv1x1Fn.apply is where the GEMM route is observed from outside, for this node too;
+        # `kept` brings back what that forward saved and its state)
+        kept = []
+        res = _Conv1x1Fn.apply(x, w, bool(training), passthrough, w16, w16t, sub, kept)
+        gemm_saved, ctx.gemm = kept
         y, part = res[0], res[1]
-        out = _BnActFn.forward(cb, y, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer,
-                               part if part.numel() else None, box)
-        ctx.save_for_backward(*ca.saved_tensors, *cb.saved_tensors)       # x, w, w16t | y, gamma32, bnbuf
-        ca.saved_tensors = cb.saved_tensors = ()
-        ctx.ca, ctx.cb, ctx.defer, ctx.nthrough = ca, cb, bool(defer), len(res) - 2
+        out, bn_saved, ctx.bn = _bn_act_forward(y, gamma, beta, running_mean, running_var, training, momentum, eps, relu, defer,
+                                                part if part.numel() else None, box)
+        ctx.save_for_backward(*gemm_saved, *bn_saved)       # x, w, w16t | y, gamma32, bnbuf
+        ctx.nthrough = len(res) - 2
         if defer:
             ctx.mark_non_differentiable(out[1])
             return (y, out[1]) + tuple(res[2:])
@@ -1934,77 +1908,60 @@ class _ConvBnFn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy, *rest):
         saved = ctx.saved_tensors
-        ca, cb = ctx.ca, ctx.cb
-        ca.saved_tensors, cb.saved_tensors = saved[:3], saved[3:]
-        try:
-            return _ConvBnFn._backward(ctx, dy, rest, saved)
-        finally:
-            # the unpacked tensors must not outlive this call on objects the node owns: the deferred output y and the
-            # passthrough x' carry this node as their grad_fn, and node -> ctx -> tensor -> node is a cycle no collector
-            # sees (the whole graph in front of it, its AccumulateGrad nodes and their streams included, would stay alive)
-            ca.saved_tensors = cb.saved_tensors = ()
-
-    @staticmethod
-    def _backward(ctx, dy, rest, saved):
+        gemm, bn = ctx.gemm, ctx.bn
         d_through = rest[-1] if ctx.nthrough else None
-        ca, cb = ctx.ca, ctx.cb
-        ca.needs_input_grad = (ctx.needs_input_grad[0], ctx.needs_input_grad[1])
-        x, w, _ = saved[:3]
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        x, w, w16t = saved[:3]
         y, gamma32, bnbuf = saved[3:]
         tail = (None,) * 13
         if dy is None:             # only the shortcut carried a gradient
-            gx = _Conv1x1Fn.backward(ca, None, None, d_through)[0]
+            gx = _conv1x1_backward(saved[:3], gemm, (need_x, need_w), None, d_through)[0]
             return (gx, None, None, None) + tail
         n, k = w.shape
         b, _, h, wd = x.shape
         m = b * h * wd
         lib, dt = L.load(), _DT[x.dtype]
         g = dy if dy.is_contiguous(memory_format=_CL) else None
-        fused = (WGRAD_BN and TIMER is None and ctx.needs_input_grad[1] and g is not None and g.dtype == y.dtype
-                 and g.data_ptr() % 16 == 0 and cb.layout == L.NHWC and w.dtype == x.dtype
-                 and ca.wdtype in (x.dtype, torch.float32) and lib.mrla_conv1x1_wgrad_bn_supported(m, k, n, dt) == 1)
+        fused = (WGRAD_BN and TIMER is None and need_w and g is not None and g.dtype == y.dtype
+                 and g.data_ptr() % 16 == 0 and bn.layout == L.NHWC and w.dtype == x.dtype
+                 and gemm.wdtype in (x.dtype, torch.float32) and lib.mrla_conv1x1_wgrad_bn_supported(m, k, n, dt) == 1)
         if not fused:              # the two backward passes as they are
-            dyc, dgamma, dbeta = _BnActFn.backward(cb, dy)[:3]
-            gx, gw = _Conv1x1Fn.backward(ca, dyc, None, d_through)[:2]
+            dyc, dgamma, dbeta = _bn_act_backward(saved[3:], bn, dy)
+            gx, gw = _conv1x1_backward(saved[:3], gemm, (need_x, need_w), dyc, d_through)
             return (gx, gw, dgamma, dbeta) + tail
         dev, st = x.device, _stream()
-        rows = cb.rows
-        handed = cb.box.take(g) if cb.box is not None else None           # (sum dz, sum dz*y) taken by the producer of dy
+        rows = bn.rows
+        handed = bn.box.take(g) if bn.box is not None else None           # (sum dz, sum dz*y) taken by the producer of dy
         if handed is not None:
             tmom, rows = handed
         else:
             tmom = torch.empty((rows, n, 2), dtype=torch.float32, device=dev)
-        small = torch.empty((5, n), dtype=torch.float32, device=dev)          # cb[n,3] | dgamma | dbeta
-        mode = L.BN_TRAIN if cb.training else L.BN_EVAL
+        kb = _BnBackward(n, dev)
+        mode = L.BN_TRAIN if bn.training else L.BN_EVAL
         if SEQUENCES:              # the sums (unless handed in) and the per-channel constants; no apply pass (dx = NULL)
-            _seq_call("mrla_bn_bwd", _ptr(g), _ptr(y), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, int(handed is not None),
-                      mode, cb.relu, _ptr(small), None, b, n, h, wd, dt, L.NHWC, st)
+            L.call("mrla_bn_bwd", _ptr(g), _ptr(y), _ptr(gamma32), _ptr(bnbuf), _ptr(tmom), rows, int(handed is not None),
+                   mode, bn.relu, _ptr(kb.small), None, b, n, h, wd, dt, L.NHWC, st)
         else:
             if handed is None:
-                L.call("mrla_bn_plane_dmoments", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), cb.relu,
+                L.call("mrla_bn_plane_dmoments", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), bn.relu,
                        _ptr(tmom), b, n, h, wd, dt, L.NHWC, st)
-            L.call("mrla_bn_stats_bwd", _ptr(tmom), _ptr(gamma32), _ptr(bnbuf[2]), _ptr(bnbuf[3]), mode, 1, _ptr(small),
-                   _ptr(small[3]), _ptr(small[4]), rows, n, m // rows, st)
+            kb.stats(tmom, gamma32, bnbuf, mode, 1, rows, n, m // rows, st)
         prow = lib.mrla_conv1x1_wgrad_rows(m, k, n, dt)
         part = torch.empty((prow, n, k), dtype=torch.float32, device=dev)
-        gw = torch.empty((n, k), dtype=ca.wdtype, device=dev)
-        if (WGRAD_BN_DX and ctx.fuse_dx and ctx.needs_input_grad[0] and d_through is None and ca.sub is None
+        gw = torch.empty((n, k), dtype=gemm.wdtype, device=dev)
+        if (WGRAD_BN_DX and ctx.fuse_dx and need_x and d_through is None and gemm.sub is None
                 and lib.mrla_conv1x1_wgrad_bn_dx_supported(m, k, n, dt) == 1):
-            # dx = dy w inside the same launch: dy never leaves the kernel (wt as _Conv1x1Fn.backward takes it)
-            w16t = saved[2]
+            # dx = dy w inside the same launch: dy never leaves the kernel (wt as _conv1x1_backward takes it)
             wt = w16t if w16t is not None else w.t().contiguous()
             gx = torch.empty_like(x)
-            L.call("mrla_conv1x1_wgrad_bn_dx", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(small), cb.relu, _ptr(x),
-                   _ptr(wt), _ptr(gx), _ptr(part), _ptr(gw), m, k, n, dt, _DT[ca.wdtype], st)
-            gw = _grad_like(gw, ca.wshape, ca.wstride)
-            return (gx, gw, small[3].to(cb.gdtype), small[4].to(cb.gdtype)) + tail
-        dyc = torch.empty_like(y)
-        L.call("mrla_conv1x1_wgrad_bn", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(small), cb.relu, _ptr(dyc),
-               _ptr(x), _ptr(part), _ptr(gw), m, k, n, dt, _DT[ca.wdtype], st)
-        ca.needs_input_grad = (ctx.needs_input_grad[0], False)
-        gx = _Conv1x1Fn.backward(ca, dyc, None, d_through)[0]
-        gw = _grad_like(gw, ca.wshape, ca.wstride)
-        return (gx, gw, small[3].to(cb.gdtype), small[4].to(cb.gdtype)) + tail
+            L.call("mrla_conv1x1_wgrad_bn_dx", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(kb.small), bn.relu, _ptr(x),
+                   _ptr(wt), _ptr(gx), _ptr(part), _ptr(gw), m, k, n, dt, _DT[gemm.wdtype], st)
+        else:
+            dyc = torch.empty_like(y)
+            L.call("mrla_conv1x1_wgrad_bn", _ptr(g), _ptr(y), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(kb.small), bn.relu, _ptr(dyc),
+                   _ptr(x), _ptr(part), _ptr(gw), m, k, n, dt, _DT[gemm.wdtype], st)
+            gx = _conv1x1_backward(saved[:3], gemm, (need_x, False), dyc, d_through)[0]
+        return (gx, _grad_like(gw, gemm.wshape, gemm.wstride)) + kb.grads(bn.gdtype) + tail
 
 
 def _conv_bn_fused(conv, bn, x, fused_bn):
@@ -2032,30 +1989,26 @@ def _eval_fold_applies(conv, bn, x, fused_bn, defer):
     return lib.mrla_conv1x1_rows(m, k, n, dt) >= 0 and lib.mrla_conv1x1_fwd_affine_supported(m, k, n, dt) == 1
 
 
+@functools.partial(_on_device, at=0)                        # (launch where the buffers live)
 def _conv_bn_eval_fold(x, w, bn, relu):
     """relu?(bn(conv1x1(x))) for an eval-mode BatchNorm2d in one GEMM launch (no autograd node: _eval_fold_applies).
     x: channels_last [b, k, h, w]; w: the [n, k] (or [n, k, 1, 1]) weight in x's dtype."""
-    if x.device.index != torch.cuda.current_device():      # (launch where the buffers live: see _on_device)
-        with torch.cuda.device(x.device):
-            return _conv_bn_eval_fold(x, w, bn, relu)
     b, k, h, wd = x.shape
     n, m = w.shape[0], b * h * wd
     dev, st, dt = x.device, _stream(), _DT[x.dtype]
     w = w.detach().reshape(n, k)
     if not w.is_contiguous():
         w = w.contiguous()
-    gamma32, beta32 = _f32(bn.weight), _f32(bn.bias)
-    rs = _RunningStats(bn.running_mean, bn.running_var, n, "conv1x1 + eval-mode BatchNorm")
-    bnbuf = torch.empty((4, n), dtype=torch.float32, device=dev)       # sc, sh, save_mean, save_inv
+    fwd = _BnForward(bn.weight, bn.bias, bn.running_mean, bn.running_var, n, L.BN_EVAL, bn.momentum or 0.0, bn.eps, dev,
+                     "conv1x1 + eval-mode BatchNorm")
+    bnbuf = fwd.bnbuf
     # (eval mode reads no sums, only the running statistics: one row of one pixel, in a buffer of its own -- the outputs are
     # __restrict__)
     amom = torch.empty((1, n, 2), dtype=torch.float32, device=dev)
-    _call("mrla_bn_stats_fwd", 0, _ptr(amom), None, _ptr(gamma32), _ptr(beta32), _ptr(rs.rm), _ptr(rs.rv), L.BN_EVAL,
-          float(bn.momentum or 0.0), float(bn.eps), _ptr(bnbuf[0]), _ptr(bnbuf[1]), _ptr(bnbuf[2]), _ptr(bnbuf[3]), 1, n, 1, st)
+    fwd.stats(amom, None, 1, n, 1, st)
     y = torch.empty((b, n, h, wd), dtype=x.dtype, device=dev, memory_format=_CL)
     _call("mrla_conv1x1_fwd_affine", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w), _ptr(bnbuf[0]),
           _ptr(bnbuf[1]), int(bool(relu)), _ptr(y), m, k, n, dt, st)
-    rs.finish(False)
     return y
 
 
@@ -2144,15 +2097,17 @@ def _own_wgrad(ctx, entry, rows_entry, dy, x, shape, taps):
     return gw
 
 
-def _stock_conv_backward(ctx, dy, x, w16, stride, padding, gx, gw):
-    """(gx, gw) with whatever is asked for and still None taken from the stock backward, masked to exactly that."""
-    need_x, need_w = ctx.needs_input_grad[0] and gx is None, ctx.needs_input_grad[1] and gw is None
-    if need_x or need_w:
-        gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
-                                                          [need_x, need_w, False])
-        gx = gx2 if need_x else gx
-        gw = gw2.to(ctx.wdtype) if need_w else gw
-    return gx, gw
+def _working_weight(ctx, x, w, for_kernel):
+    """The weight a spatial convolution node computes on: `w` cast to x's dtype as autocast casts it -- and, where one of the
+    own kernels reads it (`for_kernel`: as [n, kh, kw, c], 16 bytes a lane), channels_last and 16-byte aligned.  The
+    weight's own shape, strides and dtype are noted on `ctx` for the gradient."""
+    ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
+    w16 = w if w.dtype == x.dtype else w.to(x.dtype)
+    if for_kernel:
+        w16 = w16.contiguous(memory_format=_CL)
+        if w16.data_ptr() % 16:
+            w16 = w16.clone(memory_format=_CL)
+    return w16
 
 
 def _weight_strides(ctx, gw):
@@ -2160,6 +2115,41 @@ def _weight_strides(ctx, gw):
     if gw is not None and gw.stride() != ctx.wstride:
         gw = torch.empty_strided(ctx.wshape, ctx.wstride, dtype=gw.dtype, device=gw.device).copy_(gw)
     return gw
+
+
+_OWN_WGRAD = {3: ("mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows"), 7: ("mrla_stem_conv_wgrad", "mrla_stem_conv_wgrad_rows")}
+
+
+def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=False):
+    """(gx, gw) of a spatial convolution node that saved (x, working weight) and noted ctx.stride: the weight gradient from
+    the own kernel if `own_wgrad`; the input gradient from the own forward on the flipped, transposed weight (a pure
+    permutation) if `flipped_dgrad` at stride 1, from mrla_conv3x3_dgrad_s2 if `own_dgrad` -- each only for a gradient of x's
+    dtype at a 16-byte-aligned address; whatever is asked for and still missing from the stock backward, masked to exactly
+    that; the weight gradient in the weight's own dtype and strides (autograd's / DDP's layout contract)."""
+    x, w16 = ctx.saved_tensors
+    dy = dy.contiguous(memory_format=_CL)
+    b, c, h, wd = x.shape
+    n, k = w16.shape[0], w16.shape[2]
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
+    gx = gw = None
+    if need_w and own and own_wgrad:
+        shape = (b, c, n, h, wd, ctx.stride[0]) if k == 3 else (b, n, h, wd)
+        gw = _own_wgrad(ctx, *_OWN_WGRAD[k], dy, x, shape, (k, k, c))
+    if need_x and own and flipped_dgrad and ctx.stride[0] == 1:
+        wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
+        gx = torch.empty_like(x)
+        _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
+              b, n, c, h, wd, 1, _DT[x.dtype], _stream())
+    if need_x and own and own_dgrad:
+        gx = _own_dgrad_s2(dy, x, w16)
+    need_x, need_w = need_x and gx is None, need_w and gw is None
+    if need_x or need_w:
+        gx2, gw2, _ = torch.ops.aten.convolution_backward(dy, x, w16, None, ctx.stride, (k // 2, k // 2), (1, 1), False, (0, 0),
+                                                          1, [need_x, need_w, False])
+        gx = gx2 if need_x else gx
+        gw = gw2.to(ctx.wdtype) if need_w else gw
+    return gx, _weight_strides(ctx, gw)
 
 
 def conv3x3_applies(conv, x):
@@ -2214,30 +2204,14 @@ class _Conv3x3Fn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, w, stride, own_wgrad, own_dgrad):
         ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
-        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
-        w16 = w if w.dtype == x.dtype else w.to(x.dtype)
-        if own_dgrad:                                              # (the kernel reads the weight as [n, 3, 3, c], 16 bytes a lane)
-            w16 = w16.contiguous(memory_format=_CL)
-            if w16.data_ptr() % 16:
-                w16 = w16.clone(memory_format=_CL)
+        w16 = _working_weight(ctx, x, w, own_dgrad)
         ctx.save_for_backward(x, w16)
         return torch.ops.aten.convolution(x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1)
 
     @staticmethod
     @_on_device
     def backward(ctx, dy):
-        x, w16 = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=_CL)
-        b, c, h, wd = x.shape
-        own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
-        gx = gw = None
-        if ctx.needs_input_grad[1] and own and ctx.own_wgrad:
-            gw = _own_wgrad(ctx, "mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows", dy, x,
-                            (b, c, w16.shape[0], h, wd, ctx.stride[0]), (3, 3, c))
-        if ctx.needs_input_grad[0] and own and ctx.own_dgrad:
-            gx = _own_dgrad_s2(dy, x, w16)
-        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), gx, gw)
-        return gx, _weight_strides(ctx, gw), None, None, None
+        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, own_dgrad=ctx.own_dgrad) + (None,) * 3
 
 
 def conv3x3_fwd_applies(conv, x):
@@ -2277,10 +2251,7 @@ class _Conv3x3FwdFn(torch.autograd.Function):
     def forward(ctx, x, w, stride, moments, own_wgrad, own_dgrad):
         ctx.set_materialize_grads(False)
         ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
-        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
-        w16 = (w if w.dtype == x.dtype else w.to(x.dtype)).contiguous(memory_format=_CL)
-        if w16.data_ptr() % 16:
-            w16 = w16.clone(memory_format=_CL)
+        w16 = _working_weight(ctx, x, w, True)
         b, c, h, wd = x.shape
         n, dt = w16.shape[0], _DT[x.dtype]
         ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
@@ -2301,24 +2272,7 @@ class _Conv3x3FwdFn(torch.autograd.Function):
     def backward(ctx, dy, _dpart=None):
         if dy is None:
             return None, None, None, None, None, None
-        x, w16 = ctx.saved_tensors
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dy = dy.contiguous(memory_format=_CL)
-        b, c, h, wd = x.shape
-        n, dt = w16.shape[0], _DT[x.dtype]
-        own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
-        gx = gw = None
-        if need_w and own and ctx.own_wgrad:
-            gw = _own_wgrad(ctx, "mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows", dy, x, (b, c, n, h, wd, ctx.stride[0]), (3, 3, c))
-        if need_x and own and ctx.stride[0] == 1:
-            wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
-            gx = torch.empty_like(x)
-            _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
-                  b, n, c, h, wd, 1, dt, _stream())
-        if need_x and own and ctx.own_dgrad:
-            gx = _own_dgrad_s2(dy, x, w16)
-        gx, gw = _stock_conv_backward(ctx, dy, x, w16, ctx.stride, (1, 1), gx, gw)
-        return gx, _weight_strides(ctx, gw), None, None, None, None
+        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, flipped_dgrad=True, own_dgrad=ctx.own_dgrad) + (None,) * 4
 
 
 def _conv3x3_own(x, conv, moments):
@@ -2349,7 +2303,7 @@ def conv3x3_bn_act(x, conv, bn, relu, defer=False):
     no.  With the own forward in front of a train-mode BatchNorm2d that bn_act fuses, the convolution also returns the moment
     records of its output and bn_act takes them as `pre_moments` (the path the 1x1 GEMMs feed): no moments pass reads y back."""
     if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
-        moments = type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats and bn.training
+        moments = _is_fused_bn(bn) and bn.training
         y, part = _conv3x3_own(x, conv, moments)
         return bn_act(y, bn, relu, defer, pre_moments=part if moments else None)
     return bn_act(conv3x3(x, conv), bn, relu, defer)
@@ -2377,22 +2331,15 @@ class _StemConvFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def forward(ctx, x, w):
-        ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
-        w16 = w if w.dtype == x.dtype else w.to(x.dtype)
+        ctx.stride = (2, 2)
+        w16 = _working_weight(ctx, x, w, False)
         ctx.save_for_backward(x, w16)
-        return torch.ops.aten.convolution(x, w16, None, (2, 2), (3, 3), (1, 1), False, (0, 0), 1)
+        return torch.ops.aten.convolution(x, w16, None, ctx.stride, (3, 3), (1, 1), False, (0, 0), 1)
 
     @staticmethod
     @_on_device
     def backward(ctx, dy):
-        x, w16 = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=_CL)
-        b, _, h, wd = x.shape
-        gw = None
-        if ctx.needs_input_grad[1] and dy.dtype == x.dtype and dy.data_ptr() % 16 == 0:
-            gw = _own_wgrad(ctx, "mrla_stem_conv_wgrad", "mrla_stem_conv_wgrad_rows", dy, x, (b, w16.shape[0], h, wd), (7, 7, 3))
-        gx, gw = _stock_conv_backward(ctx, dy, x, w16, (2, 2), (3, 3), None, gw)
-        return gx, _weight_strides(ctx, gw)
+        return _spatial_conv_backward(ctx, dy, own_wgrad=True)
 
 
 def stem_conv(x, conv):
@@ -2449,7 +2396,7 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
     def second(t):                  # the second result where the convolution's own node does not produce it
         return _SubsampleFn.apply(t, subsample[0], subsample[1]) if subsample is not None else t
 
-    fused_bn = (type(bn) is torch.nn.BatchNorm2d and bn.affine and bn.track_running_stats)
+    fused_bn = _is_fused_bn(bn)
     # A strided 1x1 convolution is the stride-1 one on the subsampled input: one strided copy (a quarter of the pixels), then
     # the same GEMMs -- forward with the BatchNorm statistics in its epilogue, input gradient, weight gradient.  Not for speed
     # alone: MIOpen's input gradient of exactly these convolutions is right when launched eagerly and garbage from the second
@@ -2466,11 +2413,10 @@ def conv_bn_act(x, conv, bn, relu, defer=False, passthrough=False, subsample=Non
             out = _conv_bn_eval_fold(x.detach(), w16 if w16 is not None else wt, bn, relu)
             return (out, second(x)) if passthrough else out
         if _conv_bn_fused(conv, bn, x, fused_bn):
-            training = bn.training
-            momentum = bump_batch_counter(bn) if training else bn.momentum
+            training, momentum = _bn_step(bn)
             box = _DeferredBnBox() if defer else None
             through = passthrough and x.requires_grad
-            res = _ConvBnFn.apply(x, wt, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum or 0.0,
+            res = _ConvBnFn.apply(x, wt, bn.weight, bn.bias, bn.running_mean, bn.running_var, training, momentum,
                                   bn.eps, relu, defer, box, through, w16, w16t, subsample if through else None, fuse_dx)
             res = res if isinstance(res, tuple) else (res,)
             out = res[0]

@@ -100,7 +100,7 @@ def input_key(b, c, h, w):
 
 class recorded:
     """Every C-ABI entry the library is asked for inside the block, as (name, args), in order (functional._call and
-    functional._seq_call both go through _lib.call)."""
+    the sequence entry points both go through _lib.call)."""
 
     def __enter__(self):
         from mrla_amd import _lib as L

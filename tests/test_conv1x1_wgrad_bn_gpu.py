@@ -137,7 +137,7 @@ def _inputs(k=64, n=256, hw=8, stride=1, seed=4):
 
 class _recorded:
     """Every C-ABI entry the library is asked for inside the block, as (name, args), in order (functional._call and
-    functional._seq_call both go through _lib.call)."""
+    the sequence entry points both go through _lib.call)."""
 
     def __enter__(self):
         from mrla_amd import _lib as L
