@@ -27,6 +27,7 @@
 #include <algorithm>
 
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 #include "mrla_march.h"
 
 namespace mrla {
@@ -823,19 +824,6 @@ __global__ __launch_bounds__(kThreads) void base_value_bwd_nchw(
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-template <typename K>
-static hipError_t set_lds2(K kernel, size_t bytes) {
-  return lds_opt_in(reinterpret_cast<const void*>(kernel), bytes);
-}
-
-#define MRLA_DISPATCH_T(DT, CALL)        \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 int launch_base_gate_fwd(const float* mom, const float* wq, const float* wk, int ks, float* Kring, float* Pall,
                          float* q, int B, int C, int HW, int d, int T, int t, hipStream_t st) {
   const size_t lds = (size_t)(3 * C + 2 * ((ks - 1) / 2) + (C / d) * t) * sizeof(float);
@@ -851,15 +839,10 @@ int launch_base_attend_fwd(const void* x, const float* wv, void* Vring, const fl
   const size_t lds = (size_t)g.astride * (2 * es + sizeof(float)) + (size_t)g.CP * t * sizeof(float);
   if (lds > 150 * 1024) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL(TT)                                                                                          \
-  {                                                                                                       \
-    if (set_lds2(base_attend_fwd_nchw<TT>, lds) != hipSuccess) return MRLA_EHIP;                            \
-    hipLaunchKernelGGL((base_attend_fwd_nchw<TT>), grid, dim3(kThreads), lds, st, (const TT*)x, wv,        \
-                       (TT*)Vring, Pall, (TT*)attn, amom, g, d, T, t);                                    \
-  }
-  MRLA_DISPATCH_T(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_attend_fwd_nchw<TT>, grid, dim3(kThreads), lds, st, x, wv, Vring, Pall, attn, amom, g, d, T, t);
+  });
 }
 
 int launch_plain_bn_fwd(const float* amom, const float* gamma, const float* beta, float* run_mean, float* run_var,
@@ -892,27 +875,20 @@ int launch_base_tail_fwd(const void* x, const void* attn, const float* sc, const
   const size_t vec = 16 / dtype_size(dtype);
   const size_t want = (total / vec + kThreads - 1) / kThreads;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(want, 256 * 16));
-#define CALL(TT)                                                                                               \
-  hipLaunchKernelGGL((base_tail_fwd_nchw<TT>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x, (const TT*)attn, \
-                     sc, sh, dp, (TT*)out, total, C, HW);
-  MRLA_DISPATCH_T(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_tail_fwd_nchw<TT>, dim3(grid), dim3(kThreads), 0, st, x, attn, sc, sh, dp, out, total, C, HW);
+  });
 }
 
 int launch_base_tail_stats_bwd(const void* dout, const void* attn, const float* sc, const float* sh, const float* dp,
                                float* tmom, const SlabGeo& g, int dtype, hipStream_t st) {
   const size_t lds = (size_t)g.astride * dtype_size(dtype) * 2;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL(TT)                                                                                            \
-  {                                                                                                         \
-    if (set_lds2(base_tail_stats_bwd_nchw<TT>, lds) != hipSuccess) return MRLA_EHIP;                          \
-    hipLaunchKernelGGL((base_tail_stats_bwd_nchw<TT>), grid, dim3(kThreads), lds, st, (const TT*)dout,       \
-                       (const TT*)attn, sc, sh, dp, tmom, g);                                               \
-  }
-  MRLA_DISPATCH_T(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_tail_stats_bwd_nchw<TT>, grid, dim3(kThreads), lds, st, dout, attn, sc, sh, dp, tmom, g);
+  });
 }
 
 int launch_base_attend_bwd(const void* dout, const void* attn, const float* sc, const float* sh, const float* dp,
@@ -922,15 +898,11 @@ int launch_base_attend_bwd(const void* dout, const void* attn, const float* sc, 
   const size_t lds = (size_t)g.astride * (2 * es + sizeof(float));
   if (lds > 150 * 1024) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL(TT)                                                                                            \
-  {                                                                                                         \
-    if (set_lds2(base_attend_bwd_nchw<TT>, lds) != hipSuccess) return MRLA_EHIP;                              \
-    hipLaunchKernelGGL((base_attend_bwd_nchw<TT>), grid, dim3(kThreads), lds, st, (const TT*)dout,           \
-                       (const TT*)attn, sc, sh, dp, cb, (const TT*)Vring, (TT*)dAring, pmom, g, T, t);      \
-  }
-  MRLA_DISPATCH_T(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_attend_bwd_nchw<TT>, grid, dim3(kThreads), lds, st, dout, attn, sc, sh, dp, cb, Vring, dAring,
+                         pmom, g, T, t);
+  });
 }
 
 int launch_base_gate_bwd(const float* mom, const float* pmom, const float* Pall, const float* q, const float* Kring,
@@ -943,10 +915,8 @@ int launch_base_gate_bwd(const float* mom, const float* pmom, const float* Pall,
   const size_t staged = lds + (size_t)(C * t + 4) * sizeof(float);        // pmom[b] parked in LDS when it fits
   const int stage_pmom = staged <= 150 * 1024;
   if (stage_pmom) lds = staged;
-  if (set_lds2(base_gate_bwd_kernel, lds) != hipSuccess) return MRLA_EHIP;
-  hipLaunchKernelGGL(base_gate_bwd_kernel, dim3(B), dim3(kThreads), lds, st, mom, pmom, Pall, q, Kring, dKring, wq, wk,
-                     ks, dyx, dwqk_part, C, HW, d, T, t, first_touch, stage_pmom, tok_part, tok_bands);
-  return hip_status(hipGetLastError());
+  return launch_kernel(base_gate_bwd_kernel, dim3(B), dim3(kThreads), lds, st, mom, pmom, Pall, q, Kring, dKring, wq, wk, ks,
+                       dyx, dwqk_part, C, HW, d, T, t, first_touch, stage_pmom, tok_part, tok_bands);
 }
 
 int launch_base_value_bwd(const void* dout, const void* x, const float* wv, const void* dAring, const float* Pall,
@@ -958,23 +928,17 @@ int launch_base_value_bwd(const void* dout, const void* x, const float* wv, cons
   if (lds > 150 * 1024) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
   const int tpw = (g.NG * g.NB + kWaves - 1) / kWaves;
-#define CALL_TPW(TT, TPW)                                                                                   \
-  {                                                                                                         \
-    if (set_lds2(base_value_bwd_nchw<TT, TPW>, lds) != hipSuccess) return MRLA_EHIP;                          \
-    hipLaunchKernelGGL((base_value_bwd_nchw<TT, TPW>), grid, dim3(kThreads), lds, st, (const TT*)dout,       \
-                       (const TT*)x, wv, (const TT*)dAring, Pall, dyx, (TT*)dx, dwv_part, g, d, T, t, Tc, res);   \
-  }
-#define CALL(TT)                                                  \
-  {                                                               \
-    if (tpw <= 1) CALL_TPW(TT, 1)                                 \
-    else if (tpw == 2) CALL_TPW(TT, 2)                            \
-    else if (tpw <= kMaxTasksPerWave) CALL_TPW(TT, kMaxTasksPerWave) \
-    else return MRLA_EUNSUPPORTED;                                \
-  }
-  MRLA_DISPATCH_T(dtype, CALL)
-#undef CALL
-#undef CALL_TPW
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    auto launch = [&](auto tasks) {
+      return launch_kernel(base_value_bwd_nchw<TT, tasks()>, grid, dim3(kThreads), lds, st, dout, x, wv, dAring, Pall, dyx, dx,
+                           dwv_part, g, d, T, t, Tc, res);
+    };
+    if (tpw <= 1) return launch(Int<1>());
+    if (tpw == 2) return launch(Int<2>());
+    if (tpw <= kMaxTasksPerWave) return launch(Int<kMaxTasksPerWave>());
+    return (int)MRLA_EUNSUPPORTED;
+  });
 }
 
 }  // namespace mrla

@@ -331,27 +331,20 @@ __global__ __launch_bounds__(kThreads) void base_pmom_reduce_kernel(const float*
 // Row-marching stencil kernel, lane = channel, as light_nhwc.hip; dV arrives in the storage type from base_combine<1>.
 //   dx[r][col]  = sum_{i,k} w[i][k] * dV[r-i+1][col-k+1]
 //   dWv[i][k]  += x[r][col] * dV[r-i+1][col-k+1]      (the same window, centred on x)
-// PRE (WIDE, with the res&2 mask): the caller deferred the BatchNorm in front of the fused producer (bn3,
-// resnet_mrla_base.py:103-104,120-122) and its backward needs sum(dpre) and sum(dpre * (y3 - mean)) per channel, y3 =
-// conv3's raw output `pre`.  dpre = dx is formed here and nowhere else, so the two sums are taken here (one more owned-
-// columns row fetch per step, two accumulators; of dpre AS STORED, i.e. rounded to T): mrla_bn_plane_dmoments' 2N pass over
-// (dpre, y3) disappears -- the MRLA-light tail does the same in mrla_light_apply_bwd.
+// This is the form for the channel counts that are no multiple of 64, pixel by pixel; C % 64 == 0 runs base_value_bwd_wide on
+// the row pipeline (light_nhwc_wide.hip), which also takes the deferred-BatchNorm sums.  pre / pre_center / pre_tmom belong to
+// those sums and are not read here: they stay in the parameter list because the kernel's argument block, and with it the
+// compiled kernel, would change without them.
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool WIDE, bool PRE = false>
+template <typename T>
 __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
     const T* __restrict__ dout, const T* __restrict__ x, const float* __restrict__ wv, const T* __restrict__ dv,
     const float* __restrict__ dyx, T* __restrict__ dx, float* __restrict__ dwv_part, const T* __restrict__ pre,
     const float* __restrict__ pre_center, float* __restrict__ pre_tmom, int B, int C, int H, int W, int BG, int res) {
-  static_assert(!PRE || WIDE, "the deferred-BatchNorm sums exist on the whole-wave (C % 64 == 0) form only");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave, nwaves = blockDim.x / kWave;
   float* red = reinterpret_cast<float*>(smem_raw);
-  constexpr int FB = scratch_bytes<T>(), TB = scratch_bytes<T>();
-  unsigned char* my = smem_raw + (size_t)nwaves * 9 * kWave * sizeof(float) + (size_t)wave * (FB + 2 * TB);
-  T* scrF = reinterpret_cast<T*>(my);                      // dV gathers
-  T* scrT = reinterpret_cast<T*>(my + FB);                 // x / dOut gathers
-  T* scrS = reinterpret_cast<T*>(my + FB + TB);            // dx scatters
-  const int cbase = blockIdx.x * kWave, c = cbase + lane;
+  const int c = blockIdx.x * kWave + lane;
   const bool cv = c < C;
   const int cc = cv ? c : C - 1;
   const int nstrips = (W + kS - 1) / kS;
@@ -359,8 +352,6 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
 #pragma unroll
   for (int k = 0; k < 9; ++k) w[k] = wv[cc * 9 + k];
   float wg[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  float pm[2] = {0.f, 0.f};                          // (PRE) sum dpre, sum dpre * (y3 - center) over this workgroup's images
-  const float pcen = (PRE && pre_center) ? pre_center[cc] : 0.f;
   const float resf = (res & 1) ? 1.f : 0.f;
   const bool mask = (res & 2) != 0;
   const int b_end = min(B, (int)(blockIdx.y + 1) * BG);
@@ -369,7 +360,6 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
     const T* xi = x + ioff;
     const T* gi = dout + ioff;
     const T* ui = dv + ioff;
-    const T* pri = PRE ? pre + ioff : nullptr;
     T* dxo = dx + ioff;
     const float dy = dyx[(size_t)b * C + cc];
     for (int s = wave; s < nstrips; s += nwaves) {
@@ -377,35 +367,12 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
       float ua[kS + 2], ub[kS + 2], uc[kS + 2];                 // dV rows r-1, r, r+1 on columns s0-1 .. s0+kS
 #pragma unroll
       for (int j = 0; j < kS + 2; ++j) ua[j] = 0.f;
-      read_row<T, WIDE, kS + 2>(ui, 0, s0 - 1, H, W, C, cbase, cc, lane, scrF, ub);
-      RowLoad<T, kS + 2> qu;
-      RowLoad<T, kS> qx, qg, qp;
-      RowAddr<T, kS + 2> au;
-      RowAddr<T, kS> ax;
-      if (WIDE) {
-        make_row_addr<T, kS + 2>(au, s0 - 1, W, C, cbase, lane);
-        make_row_addr<T, kS>(ax, s0, W, C, cbase, lane);
-        issue_row<T, kS + 2>(qu, ui, 1, H, W * C, au);
-        issue_row<T, kS>(qx, xi, 0, H, W * C, ax);
-        issue_row<T, kS>(qg, gi, 0, H, W * C, ax);
-        if (PRE) issue_row<T, kS>(qp, pri, 0, H, W * C, ax);
-      }
+      read_row<T, kS + 2>(ui, 0, s0 - 1, H, W, C, cc, ub);
       for (int r = 0; r < H; ++r) {
-        float xr[kS], gr[kS], pr[kS];
-        if (WIDE) {
-          finish_row<T, kS + 2>(qu, lane, scrF, uc);
-          finish_row<T, kS>(qx, lane, scrT, xr);
-          finish_row<T, kS>(qg, lane, scrT, gr);
-          if (PRE) finish_row<T, kS>(qp, lane, scrT, pr);
-          issue_row<T, kS + 2>(qu, ui, r + 2, H, W * C, au);
-          issue_row<T, kS>(qx, xi, r + 1, H, W * C, ax);
-          issue_row<T, kS>(qg, gi, r + 1, H, W * C, ax);
-          if (PRE) issue_row<T, kS>(qp, pri, r + 1, H, W * C, ax);
-        } else {
-          read_row<T, false, kS + 2>(ui, r + 1, s0 - 1, H, W, C, cbase, cc, lane, scrF, uc);
-          read_row<T, false, kS>(xi, r, s0, H, W, C, cbase, cc, lane, scrT, xr);
-          read_row<T, false, kS>(gi, r, s0, H, W, C, cbase, cc, lane, scrT, gr);
-        }
+        float xr[kS], gr[kS];
+        read_row<T, kS + 2>(ui, r + 1, s0 - 1, H, W, C, cc, uc);
+        read_row<T, kS>(xi, r, s0, H, W, C, cc, xr);
+        read_row<T, kS>(gi, r, s0, H, W, C, cc, gr);
         float yrow[kS];
 #pragma unroll
         for (int j = 0; j < kS; ++j) {
@@ -417,11 +384,6 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
           float y = fmaf(resf, gr[j], s9 + dy);
           if (mask) y = (xr[j] > 0.f) ? y : 0.f;
           yrow[j] = y;
-          if (PRE && j < nc) {       // of dpre AS STORED (rounded to T): the BatchNorm backward must see the stored values
-            const float yq = to_f(from_f<T>(y));
-            pm[0] += yq;
-            pm[1] = fmaf(yq, pr[j] - pcen, pm[1]);
-          }
           if (j < nc) {
             const float xv = xr[j];
             wg[0] = fmaf(xv, uc[j + 2], wg[0]); wg[1] = fmaf(xv, uc[j + 1], wg[1]); wg[2] = fmaf(xv, uc[j], wg[2]);
@@ -429,7 +391,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
             wg[6] = fmaf(xv, ua[j + 2], wg[6]); wg[7] = fmaf(xv, ua[j + 1], wg[7]); wg[8] = fmaf(xv, ua[j], wg[8]);
           }
         }
-        write_row<T, WIDE, kS>(dxo, r, s0, nc, W, C, cbase, c, cv, lane, scrS, yrow);
+        write_row<T, kS>(dxo, r, s0, nc, W, C, c, cv, yrow);
 #pragma unroll
         for (int j = 0; j < kS + 2; ++j) { ua[j] = ub[j]; ub[j] = uc[j]; }
       }
@@ -439,13 +401,6 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void base_value_bwd_nhwc(
   if (wave == 0 && cv) {
 #pragma unroll
     for (int k = 0; k < 9; ++k) dwv_part[((size_t)blockIdx.y * C + c) * 9 + k] = wg[k];
-  }
-  if (PRE) {
-    wg_reduce<2>(pm, red, lane, wave, nwaves);
-    if (wave == 0 && cv) {
-      pre_tmom[((size_t)blockIdx.y * C + c) * 2 + 0] = pm[0];
-      pre_tmom[((size_t)blockIdx.y * C + c) * 2 + 1] = pm[1];
-    }
   }
 }
 
@@ -480,49 +435,38 @@ static FlatGeo flat_geo(int B, int C, int HW, int dtype, int nv) {
 int base_nhwc_tiles(int B, int C, int HW, int dtype) { return flat_geo(B, C, HW, dtype, kNVc).tiles; }
 int base_nhwc_pmom_tiles(int B, int C, int HW, int dtype) { return flat_geo(B, C, HW, dtype, kNV).tiles; }
 
-#define MRLA_DISPATCH_B(DT, CALL)        \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 int launch_base_attend_fwd_nhwc(const void* Vring, const float* Pall, void* attn, float* amom_part, int B, int C, int HW,
                                 int d, int T, int t, int dtype, hipStream_t st, int ext_gap, int ext_off) {
   if (!base_nhwc_supported(C, dtype)) return MRLA_EUNSUPPORTED;
   FlatGeo g = flat_geo(B, C, HW, dtype, kNVc);
   g.ext_gap = ext_gap; g.ext_off = ext_off;
-#define CALL(TT)                                                                                                         \
-  hipLaunchKernelGGL((base_combine_nhwc<TT, TT, 0, kNVc>), dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, (const TT*)Vring, Pall, \
-                     (TT*)attn, amom_part, g, d, T, t, t);
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_combine_nhwc<TT, TT, 0, kNVc>, dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, Vring, Pall,
+                         attn, amom_part, g, d, T, t, t);
+  });
 }
 
 int launch_base_dv_combine_nhwc(const void* dAring, const float* Pall, void* dv, int B, int C, int HW, int d, int T,
                                 int t, int Tc, int dtype, hipStream_t st) {
   if (!base_nhwc_supported(C, dtype)) return MRLA_EUNSUPPORTED;
   const FlatGeo g = flat_geo(B, C, HW, dtype, kNVc);
-#define CALL(TT)                                                                                                     \
-  hipLaunchKernelGGL((base_combine_nhwc<TT, TT, 1, kNVc>), dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, (const TT*)dAring, \
-                     Pall, (TT*)dv, (float*)nullptr, g, d, T, t, Tc);
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_combine_nhwc<TT, TT, 1, kNVc>, dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, dAring,
+                         Pall, dv, (float*)nullptr, g, d, T, t, Tc);
+  });
 }
 
 int launch_base_tail_fwd_nhwc(const void* x, const void* attn, const float* sc, const float* sh, const float* dp,
                               void* out, int B, int C, int HW, int dtype, hipStream_t st) {
   if (!base_nhwc_supported(C, dtype)) return MRLA_EUNSUPPORTED;
   const FlatGeo g = flat_geo(B, C, HW, dtype, kNV);
-#define CALL(TT)                                                                                                    \
-  hipLaunchKernelGGL((base_tail_fwd_nhwc<TT>), dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, (const TT*)x, (const TT*)attn, \
-                     sc, sh, dp, (TT*)out, g);
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_tail_fwd_nhwc<TT>, dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, x, attn, sc, sh, dp,
+                         out, g);
+  });
 }
 
 int launch_base_attend_bwd_nhwc(const void* dout, const void* attn, const float* sc, const float* sh, const float* dp,
@@ -531,14 +475,11 @@ int launch_base_attend_bwd_nhwc(const void* dout, const void* attn, const float*
   if (!base_nhwc_supported(C, dtype)) return MRLA_EUNSUPPORTED;
   FlatGeo g = flat_geo(B, C, HW, dtype, kNV);
   g.ext_gap = ext_gap; g.ext_off = ext_off;
-#define CALL_O(TT, OCC)                                                                                           \
-  hipLaunchKernelGGL((base_attend_bwd_nhwc<TT, OCC>), dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, (const TT*)dout,    \
-                     (const TT*)attn, sc, sh, dp, cb, (const TT*)Vring, (TT*)dAring, pmom_part, g, T, t);
-#define CALL(TT) { if (t <= 16) CALL_O(TT, 3) else CALL_O(TT, 1) }
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-#undef CALL_O
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto tt, auto few) {       // few steps: three workgroups per SIMD
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_attend_bwd_nhwc<TT, few() ? 3 : 1>, dim3(g.tiles, B), dim3(flat_threads(C, dtype)), 0, st, dout,
+                         attn, sc, sh, dp, cb, Vring, dAring, pmom_part, g, T, t);
+  }, t <= 16);
 }
 
 int launch_base_pmom_reduce(const float* part, float* pmom, int B, int C, int t, int tiles, hipStream_t st) {
@@ -557,20 +498,12 @@ int launch_base_value_bwd_nhwc(const void* dout, const void* x, const float* wv,
   // C % 64 == 0 runs on the LDS-DMA row pipeline (launch_base_value_bwd_wide, capi.hip); only the other channel counts come
   // here, and the deferred-BatchNorm sums (pre / pre_tmom) exist on that form only
   if (C % kWave == 0 || pre_tmom) return MRLA_EUNSUPPORTED;
-  (void)pre;
-  const size_t tb = dtype == MRLA_F32 ? scratch_bytes<float>() : scratch_bytes<bf16_t>();
-  const size_t lds = (size_t)nwaves * 9 * kWave * sizeof(float) + (size_t)nwaves * 3 * tb;
-#define CALL_W(TT, WD, PR)                                                                                          \
-  {                                                                                                                 \
-    if (set_lds_n(base_value_bwd_nhwc<TT, WD, PR>, lds) != hipSuccess) return MRLA_EHIP;                              \
-    hipLaunchKernelGGL((base_value_bwd_nhwc<TT, WD, PR>), grid, block, lds, st, (const TT*)dout, (const TT*)x, wv,     \
-                       (const TT*)dv, dyx, (TT*)dx, dwv_part, (const TT*)pre, pre_center, pre_tmom, B, C, H, W, BG, res); \
-  }
-#define CALL(TT) CALL_W(TT, false, false)
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  const size_t lds = (size_t)nwaves * 9 * kWave * sizeof(float);      // wg_reduce<9>
+  return with_dtype(dtype, [&](auto tt) {
+    using TT = typename decltype(tt)::type;
+    return launch_kernel(base_value_bwd_nhwc<TT>, grid, block, lds, st, dout, x, wv, dv, dyx, dx, dwv_part, pre,
+                         pre_center, pre_tmom, B, C, H, W, BG, res);
+  });
 }
 
 }  // namespace mrla

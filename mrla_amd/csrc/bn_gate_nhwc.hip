@@ -12,6 +12,7 @@
 
 #include "mrla_device.h"
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 
 namespace mrla {
 namespace {
@@ -230,14 +231,6 @@ __global__ __launch_bounds__(kThreads) void bn_gate_sums_bwd_kernel(const float*
 
 }  // namespace
 
-#define MRLA_GATE_DISPATCH(DT, CALL)     \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 static size_t eca_lds(int C, int ks, bool bwd) {
   const size_t cpd = (size_t)C + 2 * ((ks - 1) / 2);
   return bwd ? 2 * cpd * sizeof(float) + kWaves * sizeof(double) : cpd * sizeof(float);
@@ -263,14 +256,11 @@ int launch_bn_gate_apply(const void* y, const void* go, const float* cb, const f
   const int iters = (int)std::max<size_t>(1, std::min<size_t>((want * B + 4095) / 4096, 64));
   const dim3 grid((unsigned)((want + iters - 1) / iters), B);
   const int fixed = (kThreads * vec) % C == 0;
-#define CALL(TT)                                                                                                      \
-  if (bwd) hipLaunchKernelGGL((bn_gate_apply_kernel<TT, true>), grid, dim3(kThreads), 0, st, (const TT*)y,            \
-                              (const TT*)go, cb, sc, sh, g, q, (TT*)out, C, nv, iters, fixed);                        \
-  else     hipLaunchKernelGGL((bn_gate_apply_kernel<TT, false>), grid, dim3(kThreads), 0, st, (const TT*)y,           \
-                              (const TT*)go, cb, sc, sh, g, q, (TT*)out, C, nv, iters, fixed);
-  MRLA_GATE_DISPATCH(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto back) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(bn_gate_apply_kernel<T, back()>, grid, dim3(kThreads), 0, st, y, go, cb, sc, sh, g, q, out, C, nv,
+                         iters, fixed);
+  }, bwd != 0);
 }
 
 int launch_bn_gate_pool(const float* amom, const float* pivot, const float* sc, const float* sh, float* S, float* pooled,

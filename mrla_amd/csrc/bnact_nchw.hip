@@ -11,6 +11,7 @@
 
 #include "mrla_device.h"
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 
 namespace mrla {
 
@@ -183,41 +184,27 @@ __global__ __launch_bounds__(kThreads) void affine_act_kernel(const T* __restric
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#define MRLA_DISPATCH_B(DT, CALL)        \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 static int launch_moments(const void* x, const void* dy, const float* sc, const float* sh, int relu, float* out,
                           float* pivot, int B, int C, int HW, int dtype, int mode, hipStream_t st) {
   const int planes = B * C;
   const size_t es = dtype_size(dtype);
   if (HW >= 512) {
     const int grid = std::max(1, std::min((planes + kWaves - 1) / kWaves, 256 * 8));
-#define CALL(TT)                                                                                                  \
-  if (mode) hipLaunchKernelGGL((plane_moments_kernel<TT, 1>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,   \
-                               (const TT*)dy, sc, sh, relu, out, pivot, planes, C, HW);                           \
-  else      hipLaunchKernelGGL((plane_moments_kernel<TT, 0>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,   \
-                               (const TT*)dy, sc, sh, relu, out, pivot, planes, C, HW);
-    MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-  } else {
-    int PP = std::max(1, std::min(planes, 4096 / HW));
-    const size_t per = (((size_t)PP * HW * es + 15) / 16) * 16;
-    const size_t lds = per * (mode ? 2 : 1);
-    const int grid = std::max(1, std::min((planes + PP - 1) / PP, 256 * 8));
-#define CALL(TT)                                                                                                      \
-  if (mode) hipLaunchKernelGGL((plane_moments_small_kernel<TT, 1>), dim3(grid), dim3(kThreads), lds, st, (const TT*)x, \
-                               (const TT*)dy, sc, sh, relu, out, pivot, planes, C, HW, PP);                           \
-  else      hipLaunchKernelGGL((plane_moments_small_kernel<TT, 0>), dim3(grid), dim3(kThreads), lds, st, (const TT*)x, \
-                               (const TT*)dy, sc, sh, relu, out, pivot, planes, C, HW, PP);
-    MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
+    return with_dtype(dtype, [&](auto t, auto m) {
+      using T = typename decltype(t)::type;
+      return launch_kernel(plane_moments_kernel<T, m() ? 1 : 0>, dim3(grid), dim3(kThreads), 0, st, x, dy, sc, sh, relu, out,
+                           pivot, planes, C, HW);
+    }, mode != 0);
   }
-  return hip_status(hipGetLastError());
+  const int PP = std::max(1, std::min(planes, 4096 / HW));
+  const size_t per = (((size_t)PP * HW * es + 15) / 16) * 16;
+  const size_t lds = per * (mode ? 2 : 1);
+  const int grid = std::max(1, std::min((planes + PP - 1) / PP, 256 * 8));
+  return with_dtype(dtype, [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(plane_moments_small_kernel<T, m() ? 1 : 0>, dim3(grid), dim3(kThreads), lds, st, x, dy, sc, sh, relu,
+                         out, pivot, planes, C, HW, PP);
+  }, mode != 0);
 }
 
 int launch_plane_moments(const void* x, float* amom, float* pivot, int B, int C, int HW, int dtype, hipStream_t st) {
@@ -235,14 +222,11 @@ int launch_affine_act(const void* x, const void* dy, const float* a, const float
   const size_t vec = 16 / dtype_size(dtype);
   const size_t want = (total / vec + kThreads - 1) / kThreads;
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(want, 256 * 16));
-#define CALL(TT)                                                                                                \
-  if (bwd) hipLaunchKernelGGL((affine_act_kernel<TT, true>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,   \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C, HW);                          \
-  else     hipLaunchKernelGGL((affine_act_kernel<TT, false>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,  \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C, HW);
-  MRLA_DISPATCH_B(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto back) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(affine_act_kernel<T, back()>, dim3(grid), dim3(kThreads), 0, st, x, dy, a, sc, sh, relu, out, total,
+                         C, HW);
+  }, bwd != 0);
 }
 
 }  // namespace mrla

@@ -10,6 +10,7 @@
 
 #include "mrla_device.h"
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 
 #ifndef MRLA_REVERSE_AFFINE
 #define MRLA_REVERSE_AFFINE 1
@@ -338,14 +339,6 @@ static int flat_cw(int C, int vec) {
   return cw;
 }
 
-#define MRLA_DISPATCH_N(DT, CALL)        \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 int launch_nhwc_moments(const void* x, const void* dy, const float* sc, const float* sh, int relu, const float* dp,
                         float* out, float* pivot, int B, int C, int HW, int dtype, int mode, hipStream_t st) {
   const int vec = 16 / (int)dtype_size(dtype);
@@ -354,25 +347,19 @@ int launch_nhwc_moments(const void* x, const void* dy, const float* sc, const fl
   const int cw = flat_cw(C, vec);
   if (cw) {
     const dim3 fgrid(C / cw, B * ns);
-#define CALL(TT)                                                                                                       \
-  if (mode) hipLaunchKernelGGL((nhwc_moments_flat_kernel<TT, 1>), fgrid, dim3(kThreads), 0, st, (const TT*)x,          \
-                               (const TT*)dy, sc, sh, relu, dp, out, pivot, C, HW, ns, cw);                            \
-  else      hipLaunchKernelGGL((nhwc_moments_flat_kernel<TT, 0>), fgrid, dim3(kThreads), 0, st, (const TT*)x,          \
-                               (const TT*)dy, sc, sh, relu, dp, out, pivot, C, HW, ns, cw);
-    MRLA_DISPATCH_N(dtype, CALL)
-#undef CALL
-    return hip_status(hipGetLastError());
+    return with_dtype(dtype, [&](auto t, auto m) {
+      using T = typename decltype(t)::type;
+      return launch_kernel(nhwc_moments_flat_kernel<T, m() ? 1 : 0>, fgrid, dim3(kThreads), 0, st, x, dy, sc, sh, relu, dp, out,
+                           pivot, C, HW, ns, cw);
+    }, mode != 0);
   }
   if (dp) return MRLA_EUNSUPPORTED;                 // per-image scaling exists in the flat form only
   const dim3 grid((C + 63) / 64, B * ns);
-#define CALL(TT)                                                                                                     \
-  if (mode) hipLaunchKernelGGL((nhwc_moments_kernel<TT, 1>), grid, dim3(kThreads), 0, st, (const TT*)x, (const TT*)dy, \
-                               sc, sh, relu, out, pivot, C, HW, ns);                                                 \
-  else      hipLaunchKernelGGL((nhwc_moments_kernel<TT, 0>), grid, dim3(kThreads), 0, st, (const TT*)x, (const TT*)dy, \
-                               sc, sh, relu, out, pivot, C, HW, ns);
-  MRLA_DISPATCH_N(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto m) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(nhwc_moments_kernel<T, m() ? 1 : 0>, grid, dim3(kThreads), 0, st, x, dy, sc, sh, relu, out, pivot, C,
+                         HW, ns);
+  }, mode != 0);
 }
 
 // mom[b,c,0] = sum_hw relu(round(sc*pre + sh) + o)  (sc null: relu(pre + o)); part: [b*nhwc_bn_splits, c, 2] workspace
@@ -383,11 +370,12 @@ int launch_nhwc_pool_fused(const void* pre, const float* sc, const float* sh, co
   if (!cw) return MRLA_EUNSUPPORTED;
   const int ns = nhwc_bn_splits(B, C, HW);
   const dim3 fgrid(C / cw, B * ns);
-#define CALL(TT)                                                                                                 \
-  hipLaunchKernelGGL((nhwc_moments_flat_kernel<TT, 2>), fgrid, dim3(kThreads), 0, st, (const TT*)pre, (const TT*)o, \
-                     sc, sh, 0, (const float*)nullptr, part, (float*)nullptr, C, HW, ns, cw);
-  MRLA_DISPATCH_N(dtype, CALL)
-#undef CALL
+  const int rc = with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(nhwc_moments_flat_kernel<T, 2>, fgrid, dim3(kThreads), 0, st, pre, o, sc, sh, 0,
+                         (const float*)nullptr, part, (float*)nullptr, C, HW, ns, cw);
+  });
+  if (rc != MRLA_OK) return rc;
   hipLaunchKernelGGL(nhwc_pool_finish_kernel, dim3((B * C + kThreads - 1) / kThreads), dim3(kThreads), 0, st, part, mom,
                      B * C, C, ns);
   return hip_status(hipGetLastError());
@@ -402,24 +390,18 @@ int launch_nhwc_affine(const void* x, const void* dy, const float* a, const floa
   if ((C & (C - 1)) == 0 && C >= vec && C <= kThreads * vec) {        // power-of-two channel count: flat form
     const int iters = (int)std::max<size_t>(1, std::min<size_t>((want + 4095) / 4096, 64));
     const int fgrid = (int)((want + iters - 1) / iters);
-#define CALL(TT)                                                                                                       \
-  if (bwd) hipLaunchKernelGGL((nhwc_affine_flat_kernel<TT, true>), dim3(fgrid), dim3(kThreads), 0, st, (const TT*)x,   \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C, iters);                              \
-  else     hipLaunchKernelGGL((nhwc_affine_flat_kernel<TT, false>), dim3(fgrid), dim3(kThreads), 0, st, (const TT*)x,  \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C, iters);
-    MRLA_DISPATCH_N(dtype, CALL)
-#undef CALL
-    return hip_status(hipGetLastError());
+    return with_dtype(dtype, [&](auto t, auto back) {
+      using T = typename decltype(t)::type;
+      return launch_kernel(nhwc_affine_flat_kernel<T, back()>, dim3(fgrid), dim3(kThreads), 0, st, x, dy, a, sc, sh, relu, out,
+                           total, C, iters);
+    }, bwd != 0);
   }
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(want, 256 * 16));
-#define CALL(TT)                                                                                                   \
-  if (bwd) hipLaunchKernelGGL((nhwc_affine_kernel<TT, true>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,     \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C);                                 \
-  else     hipLaunchKernelGGL((nhwc_affine_kernel<TT, false>), dim3(grid), dim3(kThreads), 0, st, (const TT*)x,    \
-                              (const TT*)dy, a, sc, sh, relu, (TT*)out, total, C);
-  MRLA_DISPATCH_N(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto back) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(nhwc_affine_kernel<T, back()>, dim3(grid), dim3(kThreads), 0, st, x, dy, a, sc, sh, relu, out, total,
+                         C);
+  }, bwd != 0);
 }
 
 }  // namespace mrla

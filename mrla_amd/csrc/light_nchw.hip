@@ -22,6 +22,7 @@
 // apply_bwd 3 reads + 2 writes.
 #include "mrla_device.h"
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 #include "mrla_march.h"
 
 namespace mrla {
@@ -548,22 +549,6 @@ __global__ __launch_bounds__(kThreads) void light_apply_bwd_nchw(
 // ------------------------------------------------------------------------------------------------
 constexpr size_t kMaxLds = 150 * 1024;
 
-template <typename K>
-static hipError_t set_lds(K kernel, size_t bytes) {
-  return lds_opt_in(reinterpret_cast<const void*>(kernel), bytes);
-}
-
-#define MRLA_DISPATCH_AO(TT, ACT, HASO, CALL)                          \
-  if (ACT) { if (HASO) { CALL(TT, true, true); } else { CALL(TT, true, false); } } \
-  else     { if (HASO) { CALL(TT, false, true); } else { CALL(TT, false, false); } }
-#define MRLA_DISPATCH_T_ACT(DT, ACT, HASO, CALL)                       \
-  switch (DT) {                                                        \
-    case MRLA_F32:  MRLA_DISPATCH_AO(float, ACT, HASO, CALL) break;    \
-    case MRLA_BF16: MRLA_DISPATCH_AO(bf16_t, ACT, HASO, CALL) break;   \
-    case MRLA_F16:  MRLA_DISPATCH_AO(f16_t, ACT, HASO, CALL) break;    \
-    default: return MRLA_EINVAL;                                       \
-  }
-
 int launch_light_stats_fwd_nchw(const void* x, const void* o, const float* wv, float* mom, void* xout,
                                 const float* psc, const float* psh, const SlabGeo& g, int dtype, int act,
                                 hipStream_t st) {
@@ -572,21 +557,12 @@ int launch_light_stats_fwd_nchw(const void* x, const void* o, const float* wv, f
                      ((size_t)g.CP * kPT + (size_t)g.NG * g.NB * g.PW * M_N) * sizeof(float);
   if (lds > kMaxLds) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL_F(T, A, O, F)                                                                          \
-  {                                                                                                 \
-    if (set_lds(light_stats_fwd_nchw<T, A, O, F>, lds) != hipSuccess) return MRLA_EHIP;               \
-    hipLaunchKernelGGL((light_stats_fwd_nchw<T, A, O, F>), grid, dim3(kThreads), lds, st,             \
-                       (const T*)x, (const T*)o, wv, mom, (T*)xout, psc, psh, g);                   \
-  }
-#define CALL(T, A, O)                                                                               \
-  {                                                                                                 \
-    if (xout) { if (O) CALL_F(T, A, true, true) else return MRLA_EINVAL; }                          \
-    else CALL_F(T, A, O, false)                                                                     \
-  }
-  MRLA_DISPATCH_T_ACT(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_F
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto fuse) {
+    using T = typename decltype(t)::type;
+    if constexpr (fuse() && !has_o()) return (int)MRLA_EINVAL;
+    else return launch_kernel(light_stats_fwd_nchw<T, gelu(), has_o(), fuse()>, grid, dim3(kThreads), lds, st, x, o, wv, mom,
+                              xout, psc, psh, g);
+  }, act != 0, o != nullptr, xout != nullptr);
 }
 
 int launch_light_apply_fwd_nchw(const void* x, const void* o, const float* wv, const float* gate, const float* sc,
@@ -596,15 +572,11 @@ int launch_light_apply_fwd_nchw(const void* x, const void* o, const float* wv, c
   const size_t lds = (size_t)g.astride * es * 2 * (o ? 2 : 1) + (size_t)g.CP * (kPT + g.BG * kIT) * sizeof(float);
   if (lds > kMaxLds) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL(T, A, O)                                                                               \
-  {                                                                                                 \
-    if (set_lds(light_apply_fwd_nchw<T, A, O>, lds) != hipSuccess) return MRLA_EHIP;                  \
-    hipLaunchKernelGGL((light_apply_fwd_nchw<T, A, O>), grid, dim3(kThreads), lds, st, (const T*)x,   \
-                       (const T*)o, wv, gate, sc, sh, lam, dp, (T*)out, g, d, res);                 \
-  }
-  MRLA_DISPATCH_T_ACT(dtype, act, o != nullptr, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(light_apply_fwd_nchw<T, gelu(), has_o()>, grid, dim3(kThreads), lds, st, x, o, wv, gate, sc, sh, lam,
+                         dp, out, g, d, res);
+  }, act != 0, o != nullptr);
 }
 
 int launch_light_stats_bwd_nchw(const void* dout, const void* x, const void* o, const float* wv, const float* mom,
@@ -614,15 +586,10 @@ int launch_light_stats_bwd_nchw(const void* dout, const void* x, const void* o, 
                      ((size_t)g.CP * kPT + (size_t)g.NG * g.NB * g.PW * D_N) * sizeof(float);
   if (lds > kMaxLds) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL(T, A, O)                                                                               \
-  {                                                                                                 \
-    if (set_lds(light_stats_bwd_nchw<T, A, O>, lds) != hipSuccess) return MRLA_EHIP;                  \
-    hipLaunchKernelGGL((light_stats_bwd_nchw<T, A, O>), grid, dim3(kThreads), lds, st, (const T*)dout, \
-                       (const T*)x, (const T*)o, wv, mom, bmom, g);                                 \
-  }
-  MRLA_DISPATCH_T_ACT(dtype, act, o != nullptr, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(light_stats_bwd_nchw<T, gelu(), has_o()>, grid, dim3(kThreads), lds, st, dout, x, o, wv, mom, bmom, g);
+  }, act != 0, o != nullptr);
 }
 
 int launch_light_apply_bwd_nchw(const void* dout, const void* x, const void* o, const float* wv, const float* gate,
@@ -634,22 +601,12 @@ int launch_light_apply_bwd_nchw(const void* dout, const void* x, const void* o, 
                      ((size_t)g.CP * (kPT + g.BG * kIT) + (size_t)g.NG * g.NB * g.PW * 9) * sizeof(float);
   if (lds > kMaxLds) return MRLA_EUNSUPPORTED;
   const dim3 grid(g.slabs, (g.B + g.BG - 1) / g.BG);
-#define CALL_TR(T, A, O, R)                                                                         \
-  {                                                                                                 \
-    if (set_lds(light_apply_bwd_nchw<T, A, O, R>, lds) != hipSuccess) return MRLA_EHIP;               \
-    hipLaunchKernelGGL((light_apply_bwd_nchw<T, A, O, R>), grid, dim3(kThreads), lds, st,             \
-                       (const T*)dout, (const T*)x, (const T*)o, wv, gate, cb, lam, dp, dyx, (T*)dx, \
-                       (T*)dprev, dwv_part, g, d, res);                                             \
-  }
-#define CALL(T, A, O)                                                                               \
-  {                                                                                                 \
-    if (relu) { if (O && !(A)) CALL_TR(T, false, true, true) else return MRLA_EINVAL; }             \
-    else CALL_TR(T, A, O, false)                                                                    \
-  }
-  MRLA_DISPATCH_T_ACT(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_TR
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto mask) {
+    using T = typename decltype(t)::type;
+    if constexpr (mask() && (gelu() || !has_o())) return (int)MRLA_EINVAL;     // the ReLU mask: with o, without GELU
+    else return launch_kernel(light_apply_bwd_nchw<T, gelu(), has_o(), mask()>, grid, dim3(kThreads), lds, st, dout, x, o, wv,
+                              gate, cb, lam, dp, dyx, dx, dprev, dwv_part, g, d, res);
+  }, act != 0, o != nullptr, relu != 0);
 }
 
 }  // namespace mrla

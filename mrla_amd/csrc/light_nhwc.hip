@@ -11,6 +11,11 @@
 //     workgroup through LDS, in a fixed order (bitwise reproducible).
 // A workgroup = (image group, 64-channel chunk); its waves = column strips.  ResNet stage widths 56/28/14/7 give
 // 8/4/2/1 strips of exactly 7 columns.
+//
+// The kernels of this file (and light_nhwc_bwd.hip) are the FALLBACK: channel counts that are a multiple of 64 -- every
+// ResNet stage -- run on the LDS-DMA row pipeline (light_nhwc_wide.hip), to which each launcher here hands over first.  What
+// runs here are the other channel counts, pixel by pixel (ldpix / read_row / write_row of light_nhwc.h: lanes past the last
+// channel read a clamped address and store nothing).
 #include "light_nhwc.h"
 
 namespace mrla {
@@ -19,7 +24,7 @@ namespace mrla {
 // forward statistics (+ optional fused producer x = relu(pre + o), or x = relu((psc*pre + psh) + o) when the
 // per-channel affine of the BatchNorm in front (bn3) is handed over instead of being applied in a pass of its own)
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool GELU, bool HAS_O, bool FUSE, bool WIDE>
+template <typename T, bool GELU, bool HAS_O, bool FUSE>
 __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_fwd_nhwc(
     const T* __restrict__ x, const T* __restrict__ o, const float* __restrict__ wv, float* __restrict__ mom,
     T* __restrict__ xout, const float* __restrict__ psc, const float* __restrict__ psh, T* __restrict__ vout, int B,
@@ -42,26 +47,10 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_fwd_nhwc(
       const int s0 = s * kS, nc = min(kS, W - s0);
       float ra[kS + 2], rb[kS + 2], rc[kS + 2];        // x rows r-1, r, r+1 over columns s0-1 .. s0+kS
       float ob[kS + 2], oc[kS + 2];                    // o rows r, r+1 (same columns)
-      // row pieces of the NEXT load_row() call are already in flight (WIDE): software pipeline of depth one row
-      RowLoad<T, kS + 2> qx, qo;
-      RowAddr<T, kS + 2> ax, ao;
-      if (WIDE) {
-        make_row_addr<T, kS + 2>(ax, s0 - 1, W, C, cbase, lane);
-        make_row_addr<T, kS + 2>(ao, s0 - 1, W, C, cbase, lane);
-        issue_row<T, kS + 2>(qx, xi, 0, H, W * C, ax);
-        if (HAS_O) issue_row<T, kS + 2>(qo, oi, 0, H, W * C, ao);
-      }
       // loads row r into (dst, odst); FUSE forms x = relu(pre + o) and stores the owned pixels to xout
       auto load_row = [&](int r, float (&dst)[kS + 2], float (&odst)[kS + 2]) {
-        if (WIDE) {
-          finish_row<T, kS + 2>(qx, lane, SCR(0), dst);
-          if (HAS_O) finish_row<T, kS + 2>(qo, lane, SCR(1), odst);
-          issue_row<T, kS + 2>(qx, xi, r + 1, H, W * C, ax);
-          if (HAS_O) issue_row<T, kS + 2>(qo, oi, r + 1, H, W * C, ao);
-        } else {
-          read_row<T, false, kS + 2>(xi, r, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), dst);
-          if (HAS_O) read_row<T, false, kS + 2>(oi, r, s0 - 1, H, W, C, cbase, cc, lane, SCR(1), odst);
-        }
+        read_row<T, kS + 2>(xi, r, s0 - 1, H, W, C, cc, dst);
+        if (HAS_O) read_row<T, kS + 2>(oi, r, s0 - 1, H, W, C, cc, odst);
         if (FUSE) {
           if (aff) {      // BatchNorm affine of the pre-activation, rounded to T as the stand-alone pass stores it;
                           // pixels outside the image must stay zero (the padding of the 3x3 taps)
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_fwd_nhwc(
             float own[kS];
 #pragma unroll
             for (int j = 0; j < kS; ++j) own[j] = dst[j + 1];
-            write_row<T, WIDE, kS>(xo, r, s0, nc, W, C, cbase, c, cv, lane, SCR(3), own);
+            write_row<T, kS>(xo, r, s0, nc, W, C, c, cv, own);
           }
         }
       };
@@ -107,7 +96,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_fwd_nhwc(
             }
           }
         }
-        if (vo) write_row<T, WIDE, kS>(vo, r, s0, nc, W, C, cbase, c, cv, lane, SCR(3), vrow);
+        if (vo) write_row<T, kS>(vo, r, s0, nc, W, C, c, cv, vrow);
 #pragma unroll
         for (int j = 0; j < kS + 2; ++j) { ra[j] = rb[j]; rb[j] = rc[j]; ob[j] = oc[j]; }
       }
@@ -125,7 +114,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_fwd_nhwc(
 // ------------------------------------------------------------------------------------------------
 // forward apply:  out = res*x + A*V + B*o + C
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool GELU, bool HAS_O, bool WIDE>
+template <typename T, bool GELU, bool HAS_O>
 __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_nhwc(
     const T* __restrict__ x, const T* __restrict__ o, const float* __restrict__ wv, const float* __restrict__ gate,
     const float* __restrict__ sc, const float* __restrict__ sh, const float* __restrict__ lam,
@@ -156,35 +145,18 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_nhwc(
       float ra[kS + 2], rb[kS + 2], rc[kS + 2];
 #pragma unroll
       for (int j = 0; j < kS + 2; ++j) ra[j] = 0.f;
-      read_row<T, WIDE, kS + 2>(xi, 0, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), rb);
-      RowLoad<T, kS + 2> qx;
-      RowLoad<T, kS> qo;
-      RowAddr<T, kS + 2> ax;
-      RowAddr<T, kS> ao;
-      if (WIDE) {
-        make_row_addr<T, kS + 2>(ax, s0 - 1, W, C, cbase, lane);
-        make_row_addr<T, kS>(ao, s0, W, C, cbase, lane);
-        issue_row<T, kS + 2>(qx, xi, 1, H, W * C, ax);
-        if (HAS_O) issue_row<T, kS>(qo, oi, 0, H, W * C, ao);
-      }
+      read_row<T, kS + 2>(xi, 0, s0 - 1, H, W, C, cc, rb);
       for (int r = 0; r < H; ++r) {
         float ov[kS], y[kS];
-        if (WIDE) {
-          finish_row<T, kS + 2>(qx, lane, SCR(0), rc);
-          if (HAS_O) finish_row<T, kS>(qo, lane, SCR(1), ov);
-          issue_row<T, kS + 2>(qx, xi, r + 2, H, W * C, ax);
-          if (HAS_O) issue_row<T, kS>(qo, oi, r + 1, H, W * C, ao);
-        } else {
-          read_row<T, false, kS + 2>(xi, r + 1, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), rc);
-          if (HAS_O) read_row<T, false, kS>(oi, r, s0, H, W, C, cbase, cc, lane, SCR(1), ov);
-        }
+        read_row<T, kS + 2>(xi, r + 1, s0 - 1, H, W, C, cc, rc);
+        if (HAS_O) read_row<T, kS>(oi, r, s0, H, W, C, cc, ov);
 #pragma unroll
         for (int j = 0; j < kS; ++j) {
           if (GELU) y[j] = fmaf(A, gelu_f(conv_at(w, ra, rb, rc, j)), fmaf(resf, rb[j + 1], Cc));
           else      y[j] = conv_at(w, ra, rb, rc, j) + Cc;
           if (HAS_O) y[j] = fmaf(Bc, ov[j], y[j]);
         }
-        write_row<T, WIDE, kS>(yo, r, s0, nc, W, C, cbase, c, cv, lane, SCR(3), y);
+        write_row<T, kS>(yo, r, s0, nc, W, C, c, cv, y);
 #pragma unroll
         for (int j = 0; j < kS + 2; ++j) { ra[j] = rb[j]; rb[j] = rc[j]; }
       }
@@ -197,7 +169,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_nhwc(
 // shortcut (it is neither needed again nor saved when no gradient is asked for), so the block tail moves 5N instead of 6N
 // elements:  pooling pass (bnact_nhwc.hip, reads pre and o) + this pass (reads pre and o, writes out).
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool WIDE>
+template <typename T>
 __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_pre_nhwc(
     const T* __restrict__ pre, const T* __restrict__ o, const float* __restrict__ psc, const float* __restrict__ psh,
     const float* __restrict__ wv, const float* __restrict__ gate, const float* __restrict__ sc,
@@ -231,23 +203,9 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_pre_nhwc(
       const int lim = W - s0;
       float ra[kS + 2], rb[kS + 2], rc[kS + 2];          // x_t rows r-1, r, r+1 on columns s0-1 .. s0+kS
       float ob[kS + 2], oc[kS + 2];                      // o rows r, r+1
-      RowLoad<T, kS + 2> qx, qo;
-      RowAddr<T, kS + 2> ax;
-      if (WIDE) {
-        make_row_addr<T, kS + 2>(ax, s0 - 1, W, C, cbase, lane);
-        issue_row<T, kS + 2>(qx, xi, 0, H, W * C, ax);
-        issue_row<T, kS + 2>(qo, oi, 0, H, W * C, ax);
-      }
       auto form_row = [&](int r, float (&dst)[kS + 2], float (&odst)[kS + 2]) {
-        if (WIDE) {
-          finish_row<T, kS + 2>(qx, lane, SCR(0), dst);
-          finish_row<T, kS + 2>(qo, lane, SCR(1), odst);
-          issue_row<T, kS + 2>(qx, xi, r + 1, H, W * C, ax);
-          issue_row<T, kS + 2>(qo, oi, r + 1, H, W * C, ax);
-        } else {
-          read_row<T, false, kS + 2>(xi, r, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), dst);
-          read_row<T, false, kS + 2>(oi, r, s0 - 1, H, W, C, cbase, cc, lane, SCR(1), odst);
-        }
+        read_row<T, kS + 2>(xi, r, s0 - 1, H, W, C, cc, dst);
+        read_row<T, kS + 2>(oi, r, s0 - 1, H, W, C, cc, odst);
         if (aff) {
           const bool rowok = r >= 0 && r < H;
 #pragma unroll
@@ -267,7 +225,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_pre_nhwc(
         float y[kS];
 #pragma unroll
         for (int j = 0; j < kS; ++j) y[j] = fmaf(Bc, ob[j + 1], conv_at(w, ra, rb, rc, j) + Cc);
-        write_row<T, WIDE, kS>(yo, r, s0, nc, W, C, cbase, c, cv, lane, SCR(3), y);
+        write_row<T, kS>(yo, r, s0, nc, W, C, c, cv, y);
 #pragma unroll
         for (int j = 0; j < kS + 2; ++j) { ra[j] = rb[j]; rb[j] = rc[j]; ob[j] = oc[j]; }
       }
@@ -278,7 +236,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_fwd_pre_nhwc(
 // ------------------------------------------------------------------------------------------------
 // backward statistics
 // ------------------------------------------------------------------------------------------------
-template <typename T, bool GELU, bool HAS_O, bool WIDE>
+template <typename T, bool GELU, bool HAS_O>
 __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_bwd_nhwc(
     const T* __restrict__ dout, const T* __restrict__ x, const T* __restrict__ o, const float* __restrict__ wv,
     float* __restrict__ bmom, int B, int C, int H, int W, int BG) {
@@ -298,33 +256,12 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_bwd_nhwc(
       float ra[kS + 2], rb[kS + 2], rc[kS + 2];
 #pragma unroll
       for (int j = 0; j < kS + 2; ++j) ra[j] = 0.f;
-      read_row<T, WIDE, kS + 2>(xi, 0, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), rb);
-      RowLoad<T, kS + 2> qx;
-      RowLoad<T, kS> qg, qo;
-      RowAddr<T, kS + 2> ax;
-      RowAddr<T, kS> ag, ao;
-      if (WIDE) {
-        make_row_addr<T, kS + 2>(ax, s0 - 1, W, C, cbase, lane);
-        make_row_addr<T, kS>(ag, s0, W, C, cbase, lane);
-        make_row_addr<T, kS>(ao, s0, W, C, cbase, lane);
-        issue_row<T, kS + 2>(qx, xi, 1, H, W * C, ax);
-        issue_row<T, kS>(qg, gi, 0, H, W * C, ag);
-        if (HAS_O) issue_row<T, kS>(qo, oi, 0, H, W * C, ao);
-      }
+      read_row<T, kS + 2>(xi, 0, s0 - 1, H, W, C, cc, rb);
       for (int r = 0; r < H; ++r) {
         float gv[kS], ov[kS];
-        if (WIDE) {
-          finish_row<T, kS + 2>(qx, lane, SCR(0), rc);
-          finish_row<T, kS>(qg, lane, SCR(1), gv);
-          if (HAS_O) finish_row<T, kS>(qo, lane, SCR(2), ov);
-          issue_row<T, kS + 2>(qx, xi, r + 2, H, W * C, ax);
-          issue_row<T, kS>(qg, gi, r + 1, H, W * C, ag);
-          if (HAS_O) issue_row<T, kS>(qo, oi, r + 1, H, W * C, ao);
-        } else {
-          read_row<T, false, kS + 2>(xi, r + 1, s0 - 1, H, W, C, cbase, cc, lane, SCR(0), rc);
-          read_row<T, false, kS>(gi, r, s0, H, W, C, cbase, cc, lane, SCR(1), gv);
-          if (HAS_O) read_row<T, false, kS>(oi, r, s0, H, W, C, cbase, cc, lane, SCR(2), ov);
-        }
+        read_row<T, kS + 2>(xi, r + 1, s0 - 1, H, W, C, cc, rc);
+        read_row<T, kS>(gi, r, s0, H, W, C, cc, gv);
+        if (HAS_O) read_row<T, kS>(oi, r, s0, H, W, C, cc, ov);
 #pragma unroll
         for (int j = 0; j < kS; ++j) {
           if (j < nc) {
@@ -350,89 +287,55 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_stats_bwd_nhwc(
 int launch_light_stats_fwd_nhwc(const void* x, const void* o, const float* wv, float* mom, void* xout,
                                 const float* psc, const float* psh, void* vout, int B, int C, int H, int W, int dtype,
                                 int act, hipStream_t st, bool fused_no_x, int mom_ranges) {
-  const NhwcLaunch L = nhwc_launch(B, C, W, M_N, dtype);
-  if (L.wide)          // C % 64 == 0: the LDS-DMA row pipeline (light_nhwc_wide.hip)
+  if (C % kWave == 0)  // the LDS-DMA row pipeline (light_nhwc_wide.hip)
     return launch_light_stats_fwd_wide(x, o, wv, mom, xout, psc, psh, vout, B, C, H, W, dtype, act, st, fused_no_x, mom_ranges);
   if (fused_no_x) return MRLA_EUNSUPPORTED;       // (x_t stays unmaterialised on the row pipeline only)
-#define CALL_W(T, A, O, F, WD)                                                                                       \
-  {                                                                                                                  \
-    if (set_lds_n(light_stats_fwd_nhwc<T, A, O, F, WD>, L.lds) != hipSuccess) return MRLA_EHIP;                        \
-    hipLaunchKernelGGL((light_stats_fwd_nhwc<T, A, O, F, WD>), L.grid, L.block, L.lds, st, (const T*)x, (const T*)o,  \
-                       wv, mom, (T*)xout, psc, psh, (T*)vout, B, C, H, W, L.BG);                                     \
-  }
-#define CALL_F(T, A, O, F) CALL_W(T, A, O, F, false)
-#define CALL(T, A, O)                                                        \
-  {                                                                          \
-    if (xout) { if (O) CALL_F(T, A, true, true) else return MRLA_EINVAL; }   \
-    else CALL_F(T, A, O, false)                                              \
-  }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_F
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  const NhwcLaunch L = nhwc_launch(B, C, W, M_N);
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto fuse) {
+    using T = typename decltype(t)::type;
+    if constexpr (fuse() && !has_o()) return (int)MRLA_EINVAL;
+    else return launch_kernel(light_stats_fwd_nhwc<T, gelu(), has_o(), fuse()>, L.grid, L.block, L.lds, st, x, o, wv,
+                              mom, xout, psc, psh, vout, B, C, H, W, L.BG);
+  }, act != 0, o != nullptr, xout != nullptr);
 }
 
 int launch_light_apply_fwd_nhwc(const void* x, const void* o, const float* wv, const float* gate, const float* sc,
                                 const float* sh, const float* lam, const float* dp, void* out, int B, int C, int H,
                                 int W, int d, int res, int dtype, int act, hipStream_t st) {
-  const NhwcLaunch L = nhwc_launch(B, C, W, 0, dtype);
-  if (L.wide)          // C % 64 == 0: the LDS-DMA row pipeline (light_nhwc_wide.hip)
+  if (C % kWave == 0)  // the LDS-DMA row pipeline (light_nhwc_wide.hip)
     return launch_light_apply_fwd_wide(x, o, wv, gate, sc, sh, lam, dp, out, B, C, H, W, d, res, dtype, act, st);
-#define CALL_W(T, A, O, WD)                                                                                          \
-  {                                                                                                                  \
-    if (set_lds_n(light_apply_fwd_nhwc<T, A, O, WD>, L.lds) != hipSuccess) return MRLA_EHIP;                           \
-    hipLaunchKernelGGL((light_apply_fwd_nhwc<T, A, O, WD>), L.grid, L.block, L.lds, st, (const T*)x, (const T*)o, wv, \
-                       gate, sc, sh, lam, dp, (T*)out, B, C, H, W, L.BG, d, res);                                    \
-  }
-#define CALL(T, A, O) CALL_W(T, A, O, false)
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  const NhwcLaunch L = nhwc_launch(B, C, W, 0);
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(light_apply_fwd_nhwc<T, gelu(), has_o()>, L.grid, L.block, L.lds, st, x, o, wv, gate, sc, sh,
+                         lam, dp, out, B, C, H, W, L.BG, d, res);
+  }, act != 0, o != nullptr);
 }
 
 int launch_light_apply_fwd_pre_nhwc(const void* pre, const void* o, const float* psc, const float* psh, const float* wv,
                                     const float* gate, const float* sc, const float* sh, const float* lam,
                                     const float* dp, void* out, int B, int C, int H, int W, int d, int res, int dtype,
                                     hipStream_t st) {
-  const NhwcLaunch L = nhwc_launch(B, C, W, 0, dtype);
-  if (L.wide)          // C % 64 == 0: the LDS-DMA row pipeline (light_nhwc_wide.hip)
+  if (C % kWave == 0)  // the LDS-DMA row pipeline (light_nhwc_wide.hip)
     return launch_light_apply_fwd_pre_wide(pre, o, psc, psh, wv, gate, sc, sh, lam, dp, out, B, C, H, W, d, res, dtype, st);
-#define CALL_W(T, WD)                                                                                                 \
-  {                                                                                                                   \
-    if (set_lds_n(light_apply_fwd_pre_nhwc<T, WD>, L.lds) != hipSuccess) return MRLA_EHIP;                              \
-    hipLaunchKernelGGL((light_apply_fwd_pre_nhwc<T, WD>), L.grid, L.block, L.lds, st, (const T*)pre, (const T*)o, psc, \
-                       psh, wv, gate, sc, sh, lam, dp, (T*)out, B, C, H, W, L.BG, d, res);                            \
-  }
-#define CALL(T) CALL_W(T, false)
-  switch (dtype) {
-    case MRLA_F32:  CALL(float) break;
-    case MRLA_BF16: CALL(bf16_t) break;
-    case MRLA_F16:  CALL(f16_t) break;
-    default: return MRLA_EINVAL;
-  }
-#undef CALL
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  const NhwcLaunch L = nhwc_launch(B, C, W, 0);
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(light_apply_fwd_pre_nhwc<T>, L.grid, L.block, L.lds, st, pre, o, psc, psh, wv, gate, sc, sh,
+                         lam, dp, out, B, C, H, W, L.BG, d, res);
+  });
 }
 
 int launch_light_stats_bwd_nhwc(const void* dout, const void* x, const void* o, const float* wv, const float* mom,
                                 float* bmom, int B, int C, int H, int W, int dtype, int act, hipStream_t st) {
-  const NhwcLaunch L = nhwc_launch(B, C, W, D_N, dtype);
-  if (L.wide) return launch_light_stats_bwd_wide(dout, x, o, wv, mom, bmom, B, C, H, W, dtype, act, st);
+  if (C % kWave == 0) return launch_light_stats_bwd_wide(dout, x, o, wv, mom, bmom, B, C, H, W, dtype, act, st);
+  const NhwcLaunch L = nhwc_launch(B, C, W, D_N);
   // (this path's forward statistics carry zero pivots -- light_stats_fwd_nhwc -- so its raw sums ARE the shifted ones)
-#define CALL_W(T, A, O, WD)                                                                                          \
-  {                                                                                                                  \
-    if (set_lds_n(light_stats_bwd_nhwc<T, A, O, WD>, L.lds) != hipSuccess) return MRLA_EHIP;                           \
-    hipLaunchKernelGGL((light_stats_bwd_nhwc<T, A, O, WD>), L.grid, L.block, L.lds, st, (const T*)dout, (const T*)x,  \
-                       (const T*)o, wv, bmom, B, C, H, W, L.BG);                                                     \
-  }
-#define CALL(T, A, O) CALL_W(T, A, O, false)
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(light_stats_bwd_nhwc<T, gelu(), has_o()>, L.grid, L.block, L.lds, st, dout, x, o, wv, bmom,
+                         B, C, H, W, L.BG);
+  }, act != 0, o != nullptr);
 }
 
 }  // namespace mrla

@@ -12,7 +12,7 @@ namespace mrla {
 // Strip-local windows (columns relative to s0):  x rows rr-1..rr+1 over cols -2..kS+1 (kS+4 wide),
 // dU rows rr-2..rr over cols -1..kS (kS+2 wide).  At step rr: U[rr] on cols -1..kS -> dU[rr]; then dx[rr-1] on the
 // owned cols from dU rows rr-2..rr.
-template <typename T, bool GELU, bool HAS_O, bool RELU, bool WIDE>
+template <typename T, bool GELU, bool HAS_O, bool RELU>
 __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_bwd_nhwc(
     const T* __restrict__ dout, const T* __restrict__ x, const T* __restrict__ o, const float* __restrict__ wv,
     const float* __restrict__ gate, const float* __restrict__ cb, const float* __restrict__ lam,
@@ -46,40 +46,18 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_bwd_nhwc(
       float ua[kS + 2], ub[kS + 2], uc[kS + 2];      // dU rows rr-2, rr-1, rr
 #pragma unroll
       for (int j = 0; j < kS + 4; ++j) xa[j] = 0.f;
-      read_row<T, WIDE, kS + 4>(xi, 0, s0 - 2, H, W, C, cbase, cc, lane, SCR(0), xb);
+      read_row<T, kS + 4>(xi, 0, s0 - 2, H, W, C, cc, xb);
 #pragma unroll
       for (int j = 0; j < kS + 2; ++j) { ua[j] = 0.f; ub[j] = 0.f; }
-      // software pipeline (WIDE): the row pieces of step rr+1 are in flight while step rr computes
-      RowLoad<T, kS + 4> qx;
-      RowLoad<T, kS + 2> qg, qo;
-      RowAddr<T, kS + 4> ax;
-      RowAddr<T, kS + 2> ag, ao;
-      if (WIDE) {
-        make_row_addr<T, kS + 4>(ax, s0 - 2, W, C, cbase, lane);
-        make_row_addr<T, kS + 2>(ag, s0 - 1, W, C, cbase, lane);
-        make_row_addr<T, kS + 2>(ao, s0 - 1, W, C, cbase, lane);
-        issue_row<T, kS + 4>(qx, xi, 1, H, W * C, ax);
-        issue_row<T, kS + 2>(qg, gi, 0, H, W * C, ag);
-        if (HAS_O) issue_row<T, kS + 2>(qo, oi, 0, H, W * C, ao);
-      }
       // One row step.  The window arrays rotate by NAME (XA/XB/XC, UA/UB/UC, G*/D* below), three steps per loop trip,
       // so no register copies are spent on shifting the windows.
       auto step = [&](int rr, float (&XA)[kS + 4], float (&XB)[kS + 4], float (&XC)[kS + 4], float (&UA)[kS + 2],
                       float (&UB)[kS + 2], float (&UC)[kS + 2], float (&GP)[kS], float (&GC)[kS], float (&DP)[kS],
                       float (&DC)[kS]) {
         float gv[kS + 2], ov[kS + 2];                // dOut / o of row rr on columns -1 .. kS (zero outside the image)
-        if (WIDE) {
-          finish_row<T, kS + 4>(qx, lane, SCR(0), XC);
-          finish_row<T, kS + 2>(qg, lane, SCR(1), gv);
-          if (HAS_O) finish_row<T, kS + 2>(qo, lane, SCR(2), ov);
-          issue_row<T, kS + 4>(qx, xi, rr + 2, H, W * C, ax);
-          issue_row<T, kS + 2>(qg, gi, rr + 1, H, W * C, ag);
-          if (HAS_O) issue_row<T, kS + 2>(qo, oi, rr + 1, H, W * C, ao);
-        } else {
-          read_row<T, false, kS + 4>(xi, rr + 1, s0 - 2, H, W, C, cbase, cc, lane, SCR(0), XC);
-          read_row<T, false, kS + 2>(gi, rr, s0 - 1, H, W, C, cbase, cc, lane, SCR(1), gv);
-          if (HAS_O) read_row<T, false, kS + 2>(oi, rr, s0 - 1, H, W, C, cbase, cc, lane, SCR(2), ov);
-        }
+        read_row<T, kS + 4>(xi, rr + 1, s0 - 2, H, W, C, cc, XC);
+        read_row<T, kS + 2>(gi, rr, s0 - 1, H, W, C, cc, gv);
+        if (HAS_O) read_row<T, kS + 2>(oi, rr, s0 - 1, H, W, C, cc, ov);
         float dorow[kS];
         // dU[rr] on columns -1 .. kS (zero outside the image; nothing to compute on the step past the last row)
         if (rr >= H) {
@@ -113,7 +91,7 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_bwd_nhwc(
           }
           UC[j] = du;
         }
-        if (HAS_O && !RELU && rr < H) write_row<T, WIDE, kS>(doo, rr, s0, nc, W, C, cbase, c, cv, lane, SCR(4), dorow);
+        if (HAS_O && !RELU && rr < H) write_row<T, kS>(doo, rr, s0, nc, W, C, c, cv, dorow);
         // dx[rr-1] on the owned columns:  dx[ro][col] = sum_{i,k} w[i][k] * dU[ro-i+1][col-k+1]
         if (rr >= 1) {
           const int ro = rr - 1;
@@ -130,8 +108,8 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void light_apply_bwd_nhwc(
             yrow[j] = y;
             dsum[j] = DP[j] + y;
           }
-          write_row<T, WIDE, kS>(dxo, ro, s0, nc, W, C, cbase, c, cv, lane, SCR(3), yrow);
-          if (RELU && HAS_O) write_row<T, WIDE, kS>(doo, ro, s0, nc, W, C, cbase, c, cv, lane, SCR(4), dsum);
+          write_row<T, kS>(dxo, ro, s0, nc, W, C, c, cv, yrow);
+          if (RELU && HAS_O) write_row<T, kS>(doo, ro, s0, nc, W, C, c, cv, dsum);
         }
       };
       float g0[kS], g1[kS], g2[kS], d0[kS], d1[kS], d2[kS];
@@ -166,31 +144,19 @@ int launch_light_apply_bwd_nhwc(const void* dout, const void* x, const void* o, 
                                 const float* cb, const float* lam, const float* dp, const float* dyx, void* dx,
                                 void* dprev, float* dwv_part, const void* pre, const float* pre_center, float* pre_tmom,
                                 int B, int C, int H, int W, int d, int res, int relu, int dtype, int act, hipStream_t st) {
-  NhwcLaunch L = nhwc_launch(B, C, W, 9, dtype);
-  if (L.wide)          // C % 64 == 0: the LDS-DMA row pipeline (light_nhwc_wide.hip)
+  if (C % kWave == 0)  // the LDS-DMA row pipeline (light_nhwc_wide.hip)
     return launch_light_apply_bwd_wide(dout, x, o, wv, gate, cb, lam, dp, dyx, dx, dprev, dwv_part, pre, pre_center, pre_tmom,
                                        B, C, H, W, d, res, relu, dtype, act, st);
   if (pre_tmom) return MRLA_EUNSUPPORTED;       // (the deferred-BatchNorm sums exist on the row pipeline only)
+  NhwcLaunch L = nhwc_launch(B, C, W, 9);
   L.BG = nhwc_images_per_group(B, C, W);                  // = the rows mrla_light_wgrad_rows() promised
   L.grid = dim3(L.grid.x, (B + L.BG - 1) / L.BG);
-#define CALL_W(T, A, O, R, WD)                                                                                       \
-  {                                                                                                                  \
-    if (set_lds_n(light_apply_bwd_nhwc<T, A, O, R, WD>, L.lds) != hipSuccess) return MRLA_EHIP;                        \
-    hipLaunchKernelGGL((light_apply_bwd_nhwc<T, A, O, R, WD>), L.grid, L.block, L.lds, st, (const T*)dout,            \
-                       (const T*)x, (const T*)o, wv, gate, cb, lam, dp, dyx, (T*)dx, (T*)dprev, dwv_part, B, C, H, W, \
-                       L.BG, d, res);                                                                                \
-  }
-#define CALL_R(T, A, O, R) CALL_W(T, A, O, R, false)
-#define CALL(T, A, O)                                                                        \
-  {                                                                                          \
-    if (relu) { if (O && !(A)) CALL_R(T, false, true, true) else return MRLA_EINVAL; }       \
-    else CALL_R(T, A, O, false)                                                              \
-  }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_R
-#undef CALL_W
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto mask) {
+    using T = typename decltype(t)::type;
+    if constexpr (mask() && (gelu() || !has_o())) return (int)MRLA_EINVAL;     // the ReLU mask: with o, without GELU
+    else return launch_kernel(light_apply_bwd_nhwc<T, gelu(), has_o(), mask()>, L.grid, L.block, L.lds, st, dout, x, o,
+                              wv, gate, cb, lam, dp, dyx, dx, dprev, dwv_part, B, C, H, W, L.BG, d, res);
+  }, act != 0, o != nullptr, relu != 0);
 }
 
 }  // namespace mrla

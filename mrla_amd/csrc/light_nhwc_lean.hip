@@ -358,21 +358,15 @@ int launch_light_stats_bwd_lean_wide(const void* dout, const void* pre, const vo
                                      hipStream_t st) {
   if (!light_lean_supported(B, C, H, W, dtype)) return MRLA_EUNSUPPORTED;
   const bool ragged = (W % kS) != 0;
-#define CALL_K(T, AF, RG)                                                                                          \
-  {                                                                                                                \
-    const WideLaunch L = wide_launch(P_STATS_BWD, B, C, W, D_N, stats_bwd_lean_wave_bytes<T>(), 0, false, nhwc_bmom_zranges(B, C, H, W).strips); \
-    if (set_lds_n(light_stats_bwd_lean_wide<T, AF, RG>, L.lds) != hipSuccess) return MRLA_EHIP;                     \
-    hipLaunchKernelGGL((light_stats_bwd_lean_wide<T, AF, RG>), L.grid, L.block, L.lds, st, (const T*)dout,          \
-                       (const T*)pre, (const T*)o, wv, psc, psh, mom, bmom, B, C, H, W, L.BG, L.wc);               \
-  }
-#define CALL_A(T, AF) { if (ragged) CALL_K(T, AF, true) else CALL_K(T, AF, false) }
-#define CALL(T) { if (psc) CALL_A(T, true) else CALL_A(T, false) }
-  if (dtype == MRLA_BF16) CALL(bf16_t) else CALL(f16_t)
-#undef CALL
-#undef CALL_A
-#undef CALL_K
-  if (hipGetLastError() != hipSuccess) return MRLA_EHIP;
-  return launch_fold_rows(bmom, nhwc_bmom_zranges(B, C, H, W).strips, B * C * D_N, st);      // partial records -> record 0
+  const int nz = nhwc_bmom_zranges(B, C, H, W).strips;
+  const int rc = with_dtype16(dtype, [&](auto t, auto aff, auto rg) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_STATS_BWD, B, C, W, D_N, stats_bwd_lean_wave_bytes<T>(), 0, false, nz);
+    return launch_kernel(light_stats_bwd_lean_wide<T, aff(), rg()>, L.grid, L.block, L.lds, st, dout, pre, o, wv, psc, psh,
+                         mom, bmom, B, C, H, W, L.BG, L.wc);
+  }, psc != nullptr, ragged);
+  if (rc != MRLA_OK) return rc;
+  return launch_fold_rows(bmom, nz, B * C * D_N, st);      // partial records -> record 0
 }
 
 int launch_light_apply_bwd_lean_wide(const void* dout, const void* pre, const void* o, const float* wv, const float* psc,
@@ -384,23 +378,13 @@ int launch_light_apply_bwd_lean_wide(const void* dout, const void* pre, const vo
   const bool ragged = (W % kS) != 0;
   const int bg = nhwc_images_per_group(B, C, W);          // image groups x strip ranges = the rows mrla_light_wgrad_rows() promised
   const int nz = nhwc_wgrad_zranges(B, C, H, W).strips;
-#define CALL_K(T, AF, RG, PR)                                                                                      \
-  {                                                                                                                \
-    const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, apply_bwd_lean_wave_bytes<T>(), bg, false, nz);      \
-    if (set_lds_n(light_apply_bwd_lean_wide<T, AF, RG, PR>, L.lds) != hipSuccess) return MRLA_EHIP;                 \
-    hipLaunchKernelGGL((light_apply_bwd_lean_wide<T, AF, RG, PR>), L.grid, L.block, L.lds, st, (const T*)dout,      \
-                       (const T*)pre, (const T*)o, wv, psc, psh, gate, cb, lam, dp, dyx, (T*)dx, (T*)dprev,         \
-                       dwv_part, pre_center, pre_tmom, B, C, H, W, L.BG, d, res, L.wc);                            \
-  }
-#define CALL_P(T, AF, RG) { if (pre_tmom) CALL_K(T, AF, RG, true) else CALL_K(T, AF, RG, false) }
-#define CALL_A(T, AF) { if (ragged) CALL_P(T, AF, true) else CALL_P(T, AF, false) }
-#define CALL(T) { if (psc) CALL_A(T, true) else CALL_A(T, false) }
-  if (dtype == MRLA_BF16) CALL(bf16_t) else CALL(f16_t)
-#undef CALL
-#undef CALL_A
-#undef CALL_P
-#undef CALL_K
-  return hip_status(hipGetLastError());
+  return with_dtype16(dtype, [&](auto t, auto aff, auto rg, auto sums) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, apply_bwd_lean_wave_bytes<T>(), bg, false, nz);
+    return launch_kernel(light_apply_bwd_lean_wide<T, aff(), rg(), sums()>, L.grid, L.block, L.lds, st, dout, pre, o, wv,
+                         psc, psh, gate, cb, lam, dp, dyx, dx, dprev, dwv_part, pre_center, pre_tmom, B, C, H, W, L.BG, d,
+                         res, L.wc);
+  }, psc != nullptr, ragged, pre_tmom != nullptr);
 }
 
 }  // namespace mrla

@@ -946,61 +946,31 @@ int launch_light_stats_fwd_wide(const void* x, const void* o, const float* wv, f
     if (zr.strips * zr.rows != mom_ranges) return MRLA_EINVAL;
   }
   const int nz = zr.strips, nzr = zr.rows;
-  auto merged = [&](int ws) {
-    if (nz * nzr > 1)
-      hipLaunchKernelGGL(light_mom_merge_kernel, dim3((B * C + kThreads - 1) / kThreads), dim3(kThreads), 0, st, mom, B, C, H, W,
-                         ws, nz, nzr);
-    return hip_status(hipGetLastError());
-  };
-  int ws_used = 1;
+  const bool stream = stream_fetches(B, C, H, W, dtype_size(dtype));
+  int ws_used = 1, rc;
   if (xout || fused_no_x) {       // the fused producer (needs o, no activation on V); fused_no_x: x_t is not written
     if (!o || act) return MRLA_EINVAL;
-#define CALL_C(KERNEL, T, AF, RG, NT, SX, CT)                                                                       \
-  {                                                                                                                 \
-    if (set_lds_n(KERNEL<T, AF, RG, NT, SX, CT>, L.lds) != hipSuccess) return MRLA_EHIP;                             \
-    hipLaunchKernelGGL((KERNEL<T, AF, RG, NT, SX, CT>), L.grid, L.block, L.lds, st, (const T*)x, (const T*)o, wv, mom, \
-                       (T*)xout, psc, psh, (T*)vout, B, C, H, W, L.BG, L.wc, nzr);                                  \
+    rc = with_dtype(dtype, [&](auto t, auto aff, auto rg, auto nt, auto store_x, auto cut) {
+      using T = typename decltype(t)::type;
+      const WideLaunch L = wide_launch(P_STATS_FUSED, B, C, W, kMomRed, fused_wave_bytes<T>(), bg, false, nz, nzr);
+      ws_used = (int)(L.block.x / kWave) / L.wc;
+      return launch_kernel(light_stats_fwd_fused_wide<T, aff(), rg(), nt() ? 2 : 0, store_x(), cut()>, L.grid, L.block, L.lds,
+                           st, x, o, wv, mom, xout, psc, psh, vout, B, C, H, W, L.BG, L.wc, nzr);
+    }, psc != nullptr, ragged, stream, xout != nullptr, nzr > 1);
+  } else {
+    rc = with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto rg, auto cut) {
+      using T = typename decltype(t)::type;
+      const WideLaunch L = wide_launch(P_STATS_FWD, B, C, W, kMomRed, stats_fwd_wave_bytes<T>(), bg, false, nz, nzr);
+      ws_used = (int)(L.block.x / kWave) / L.wc;
+      return launch_kernel(light_stats_fwd_wide<T, gelu(), has_o(), rg(), cut()>, L.grid, L.block, L.lds, st, x, o, wv, mom,
+                           vout, B, C, H, W, L.BG, L.wc, nzr);
+    }, act != 0, o != nullptr, ragged, nzr > 1);
   }
-#define CALL_K(KERNEL, T, AF, RG, NT, SX) { if (nzr > 1) CALL_C(KERNEL, T, AF, RG, NT, SX, true) else CALL_C(KERNEL, T, AF, RG, NT, SX, false) }
-#define CALL_N(T, AF, RG, NT)                                                                                       \
-  {                                                                                                                 \
-    const WideLaunch L = wide_launch(P_STATS_FUSED, B, C, W, kMomRed, fused_wave_bytes<T>(), bg, false, nz, nzr);   \
-    ws_used = (int)(L.block.x / kWave) / L.wc;                                                                      \
-    if (xout) CALL_K(light_stats_fwd_fused_wide, T, AF, RG, NT, true)                                               \
-    else CALL_K(light_stats_fwd_fused_wide, T, AF, RG, NT, false)                                                   \
-  }
-#define CALL_R(T, AF, RG) { if (stream_fetches(B, C, H, W, sizeof(T))) CALL_N(T, AF, RG, 2) else CALL_N(T, AF, RG, 0) }
-#define CALL_A(T, AF) { if (ragged) CALL_R(T, AF, true) else CALL_R(T, AF, false) }
-#define CALL(T) { if (psc) CALL_A(T, true) else CALL_A(T, false) }
-    switch (dtype) {
-      case MRLA_F32:  CALL(float) break;
-      case MRLA_BF16: CALL(bf16_t) break;
-      case MRLA_F16:  CALL(f16_t) break;
-      default: return MRLA_EINVAL;
-    }
-#undef CALL
-#undef CALL_A
-#undef CALL_R
-#undef CALL_N
-#undef CALL_K
-#undef CALL_C
-    return merged(ws_used);
-  }
-#define CALL_C(T, A, O, RG, CT)                                                                                     \
-  {                                                                                                                 \
-    const WideLaunch L = wide_launch(P_STATS_FWD, B, C, W, kMomRed, stats_fwd_wave_bytes<T>(), bg, false, nz, nzr); \
-    ws_used = (int)(L.block.x / kWave) / L.wc;                                                                      \
-    if (set_lds_n(light_stats_fwd_wide<T, A, O, RG, CT>, L.lds) != hipSuccess) return MRLA_EHIP;                     \
-    hipLaunchKernelGGL((light_stats_fwd_wide<T, A, O, RG, CT>), L.grid, L.block, L.lds, st, (const T*)x, (const T*)o, wv, \
-                       mom, (T*)vout, B, C, H, W, L.BG, L.wc, nzr);                                                 \
-  }
-#define CALL_R(T, A, O, RG) { if (nzr > 1) CALL_C(T, A, O, RG, true) else CALL_C(T, A, O, RG, false) }
-#define CALL(T, A, O) { if (ragged) CALL_R(T, A, O, true) else CALL_R(T, A, O, false) }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_R
-#undef CALL_C
-  return merged(ws_used);
+  if (rc != MRLA_OK) return rc;
+  if (nz * nzr > 1)               // the ranges' records -> record 0
+    hipLaunchKernelGGL(light_mom_merge_kernel, dim3((B * C + kThreads - 1) / kThreads), dim3(kThreads), 0, st, mom, B, C, H, W,
+                       ws_used, nz, nzr);
+  return hip_status(hipGetLastError());
 }
 
 int launch_light_apply_fwd_wide(const void* x, const void* o, const float* wv, const float* gate, const float* sc,
@@ -1008,20 +978,12 @@ int launch_light_apply_fwd_wide(const void* x, const void* o, const float* wv, c
                                 int W, int d, int res, int dtype, int act, hipStream_t st) {
   // (no sums: every strip round has its own workgroup; the rows are cut as well where that still leaves CUs idle)
   const int nzr = wide_row_ranges(wide_workgroups(P_APPLY_FWD, B, C, W, 0, wide_strip_rounds(P_APPLY_FWD, C, W)), H, (long)B * C * H * W);
-#define CALL(T, A, O) { if (stream_fetches(B, C, H, W, sizeof(T))) CALL_N(T, A, O, 2) else CALL_N(T, A, O, 0) }
-#define CALL_N(T, A, O, NT) { if (nzr > 1) CALL_C(T, A, O, NT, true) else CALL_C(T, A, O, NT, false) }
-#define CALL_C(T, A, O, NT, CT)                                                                                    \
-  {                                                                                                                \
-    const WideLaunch L = wide_launch(P_APPLY_FWD, B, C, W, 0, apply_fwd_wave_bytes<T>(), 0, true, 1, nzr);         \
-    if (set_lds_n(light_apply_fwd_wide<T, A, O, NT, CT>, L.lds) != hipSuccess) return MRLA_EHIP;                    \
-    hipLaunchKernelGGL((light_apply_fwd_wide<T, A, O, NT, CT>), L.grid, L.block, L.lds, st, (const T*)x, (const T*)o, wv, \
-                       gate, sc, sh, lam, dp, (T*)out, B, C, H, W, L.BG, d, res, L.wc, nzr);                       \
-  }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_N
-#undef CALL_C
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto nt, auto cut) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_APPLY_FWD, B, C, W, 0, apply_fwd_wave_bytes<T>(), 0, true, 1, nzr);
+    return launch_kernel(light_apply_fwd_wide<T, gelu(), has_o(), nt() ? 2 : 0, cut()>, L.grid, L.block, L.lds, st, x, o, wv,
+                         gate, sc, sh, lam, dp, out, B, C, H, W, L.BG, d, res, L.wc, nzr);
+  }, act != 0, o != nullptr, stream_fetches(B, C, H, W, dtype_size(dtype)), nzr > 1);
 }
 
 int launch_light_apply_fwd_pre_wide(const void* pre, const void* o, const float* psc, const float* psh, const float* wv,
@@ -1029,25 +991,12 @@ int launch_light_apply_fwd_pre_wide(const void* pre, const void* o, const float*
                                     const float* dp, void* out, int B, int C, int H, int W, int d, int res, int dtype,
                                     hipStream_t st) {
   const int nzr = wide_row_ranges(wide_workgroups(P_APPLY_FWD, B, C, W, 0, wide_strip_rounds(P_APPLY_FWD, C, W)), H, (long)B * C * H * W);
-#define CALL_C(T, AF, CT)                                                                                            \
-  {                                                                                                                  \
-    const WideLaunch L = wide_launch(P_APPLY_FWD, B, C, W, 0, fused_wave_bytes<T>(), 0, true, 1, nzr);               \
-    if (set_lds_n(light_apply_fwd_pre_wide<T, AF, CT>, L.lds) != hipSuccess) return MRLA_EHIP;                        \
-    hipLaunchKernelGGL((light_apply_fwd_pre_wide<T, AF, CT>), L.grid, L.block, L.lds, st, (const T*)pre, (const T*)o, psc, \
-                       psh, wv, gate, sc, sh, lam, dp, (T*)out, B, C, H, W, L.BG, d, res, L.wc, nzr);                \
-  }
-#define CALL_A(T, AF) { if (nzr > 1) CALL_C(T, AF, true) else CALL_C(T, AF, false) }
-#define CALL(T) { if (psc) CALL_A(T, true) else CALL_A(T, false) }
-  switch (dtype) {
-    case MRLA_F32:  CALL(float) break;
-    case MRLA_BF16: CALL(bf16_t) break;
-    case MRLA_F16:  CALL(f16_t) break;
-    default: return MRLA_EINVAL;
-  }
-#undef CALL
-#undef CALL_A
-#undef CALL_C
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto aff, auto cut) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_APPLY_FWD, B, C, W, 0, fused_wave_bytes<T>(), 0, true, 1, nzr);
+    return launch_kernel(light_apply_fwd_pre_wide<T, aff(), cut()>, L.grid, L.block, L.lds, st, pre, o, psc, psh, wv, gate,
+                         sc, sh, lam, dp, out, B, C, H, W, L.BG, d, res, L.wc, nzr);
+  }, psc != nullptr, nzr > 1);
 }
 
 
@@ -1061,71 +1010,40 @@ int launch_light_apply_bwd_wide(const void* dout, const void* x, const void* o, 
   const int nz = zr.strips, nzr = zr.rows;
   if (pre_tmom && (!pre || !relu)) return MRLA_EINVAL;
   if (pre_tmom && dtype == MRLA_F32) return MRLA_EUNSUPPORTED;      // (LDS: see mrla_light_apply_bwd_pre_sums)
-#define CALL_CUT(T, A, O, R, RG, PR, CT)                                                                             \
-  {                                                                                                                  \
-    const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, apply_bwd_wave_bytes<T, PR>(), bg, false, nz, nzr);    \
-    if (set_lds_n(light_apply_bwd_wide<T, A, O, R, RG, PR, CT>, L.lds) != hipSuccess) return MRLA_EHIP;               \
-    hipLaunchKernelGGL((light_apply_bwd_wide<T, A, O, R, RG, PR, CT>), L.grid, L.block, L.lds, st, (const T*)dout,    \
-                       (const T*)x, (const T*)o, wv, gate, cb, lam, dp, dyx, (T*)dx, (T*)dprev, dwv_part,             \
-                       (const T*)pre, pre_center, pre_tmom, B, C, H, W, L.BG, d, res, L.wc, nzr);                     \
-  }
-#define CALL_PLAIN(T, A, O, R, RG, PR) { if (nzr > 1) CALL_CUT(T, A, O, R, RG, PR, true) else CALL_CUT(T, A, O, R, RG, PR, false) }
+  return with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto mask, auto rg, auto sums, auto cut) {
+    using T = typename decltype(t)::type;
+    if constexpr (mask() && (gelu() || !has_o())) return (int)MRLA_EINVAL;        // the ReLU mask: with o, without GELU
+    else if constexpr (sums() && !mask()) return (int)MRLA_EINVAL;               // (refused above)
+    else if constexpr (sums() && sizeof(T) != 2) return (int)MRLA_EUNSUPPORTED;  // (refused above)
+    else {
 #if MRLA_APPLY_BWD_PK
-#define CALL_G(T, A, O, R, RG, PR)                                                                                   \
-  {                                                                                                                  \
-    if (!(A) && nzr == 1) {                                                                                          \
-      constexpr int DP = sizeof(T) == 2 ? MRLA_APPLY_BWD_DEPTH : 1;                                                  \
-      const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 0, apply_bwd_pk_wave_bytes<T, PR, DP>(), bg, false, nz); \
-      if (set_lds_n(light_apply_bwd_wide_pk<T, O, R, RG, PR, DP>, L.lds) != hipSuccess) return MRLA_EHIP;             \
-      hipLaunchKernelGGL((light_apply_bwd_wide_pk<T, O, R, RG, PR, DP>), L.grid, L.block, L.lds, st, (const T*)dout,  \
-                         (const T*)x, (const T*)o, wv, gate, cb, lam, dp, dyx, (T*)dx, (T*)dprev, dwv_part,           \
-                         (const T*)pre, pre_center, pre_tmom, B, C, H, W, L.BG, d, res, L.wc);                        \
-    } else CALL_PLAIN(T, A, O, R, RG, PR)                                                                            \
-  }
-#else
-#define CALL_G(T, A, O, R, RG, PR) CALL_PLAIN(T, A, O, R, RG, PR)
+      if constexpr (!gelu() && !cut()) {
+        constexpr int DP = sizeof(T) == 2 ? MRLA_APPLY_BWD_DEPTH : 1;
+        const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 0, apply_bwd_pk_wave_bytes<T, sums(), DP>(), bg, false, nz);
+        return launch_kernel(light_apply_bwd_wide_pk<T, has_o(), mask(), rg(), sums(), DP>, L.grid, L.block, L.lds, st, dout,
+                             x, o, wv, gate, cb, lam, dp, dyx, dx, dprev, dwv_part, pre, pre_center, pre_tmom, B, C, H, W,
+                             L.BG, d, res, L.wc);
+      }
 #endif
-#define CALL_R(T, A, O, R) { if (ragged) CALL_G(T, A, O, R, true, false) else CALL_G(T, A, O, R, false, false) }
-#define CALL_P(T)                                                                                       \
-  {                                                                                                     \
-    if constexpr (sizeof(T) == 2) {                                                                     \
-      if (ragged) CALL_G(T, false, true, true, true, true) else CALL_G(T, false, true, true, false, true) \
-    }                                                                                                   \
-  }
-#define CALL(T, A, O)                                                                        \
-  {                                                                                          \
-    if (relu) {                                                                              \
-      if (!(O && !(A))) return MRLA_EINVAL;                                                  \
-      if (pre_tmom) CALL_P(T) else CALL_R(T, false, true, true)                              \
-    } else CALL_R(T, A, O, false)                                                            \
-  }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_P
-#undef CALL_R
-#undef CALL_G
-#undef CALL_PLAIN
-#undef CALL_CUT
-  return hip_status(hipGetLastError());
+      const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, apply_bwd_wave_bytes<T, sums()>(), bg, false, nz, nzr);
+      return launch_kernel(light_apply_bwd_wide<T, gelu(), has_o(), mask(), rg(), sums(), cut()>, L.grid, L.block, L.lds, st,
+                           dout, x, o, wv, gate, cb, lam, dp, dyx, dx, dprev, dwv_part, pre, pre_center, pre_tmom, B, C, H,
+                           W, L.BG, d, res, L.wc, nzr);
+    }
+  }, act != 0, o != nullptr, relu != 0, ragged, pre_tmom != nullptr, nzr > 1);
 }
 
 int launch_light_stats_bwd_wide(const void* dout, const void* x, const void* o, const float* wv, const float* mom,
                                 float* bmom, int B, int C, int H, int W, int dtype, int act, hipStream_t st) {
-#define CALL(T, A, O) CALL_N(T, A, O, 0)      /* default policy: apply_bwd re-reads these tensors right after */
   const ZRanges zr = nhwc_bmom_zranges(B, C, H, W);
-#define CALL_N(T, A, O, NT) { if (zr.rows > 1) CALL_C(T, A, O, NT, true) else CALL_C(T, A, O, NT, false) }
-#define CALL_C(T, A, O, NT, CT)                                                                                    \
-  {                                                                                                                \
-    const WideLaunch L = wide_launch(P_STATS_BWD, B, C, W, D_N, stats_bwd_wave_bytes<T>(), 0, false, zr.strips, zr.rows); \
-    if (set_lds_n(light_stats_bwd_wide<T, A, O, NT, CT>, L.lds) != hipSuccess) return MRLA_EHIP;                    \
-    hipLaunchKernelGGL((light_stats_bwd_wide<T, A, O, NT, CT>), L.grid, L.block, L.lds, st, (const T*)dout, (const T*)x, \
-                       (const T*)o, wv, mom, bmom, B, C, H, W, L.BG, L.wc, zr.rows);                               \
-  }
-  MRLA_DISPATCH_T_N(dtype, act, o != nullptr, CALL)
-#undef CALL
-#undef CALL_N
-#undef CALL_C
-  if (hipGetLastError() != hipSuccess) return MRLA_EHIP;
+  // (fetches with the default cache policy: apply_bwd re-reads these tensors right after)
+  const int rc = with_dtype(dtype, [&](auto t, auto gelu, auto has_o, auto cut) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_STATS_BWD, B, C, W, D_N, stats_bwd_wave_bytes<T>(), 0, false, zr.strips, zr.rows);
+    return launch_kernel(light_stats_bwd_wide<T, gelu(), has_o(), 0, cut()>, L.grid, L.block, L.lds, st, dout, x, o, wv, mom,
+                         bmom, B, C, H, W, L.BG, L.wc, zr.rows);
+  }, act != 0, o != nullptr, zr.rows > 1);
+  if (rc != MRLA_OK) return rc;
   // the ranges' partial records -> record 0, the one mrla_light_bn_bwd / mrla_light_gate_bwd read
   return launch_fold_rows(bmom, zr.strips * zr.rows, B * C * D_N, st);
 }
@@ -1152,23 +1070,12 @@ int launch_base_value_bwd_wide(const void* dout, const void* x, const float* wv,
     hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((n1 + n2 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
                        dwv_part + used * C * 9, n1, pre_tmom ? pre_tmom + used * C * 2 : nullptr, n2);
   }
-#define CALL_P(T, PR)                                                                                               \
-  {                                                                                                                 \
-    const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, base_vbwd_wave_bytes<T, PR>(), bg, false, nz);                             \
-    if (set_lds_n(base_value_bwd_wide<T, PR>, L.lds) != hipSuccess) return MRLA_EHIP;                                \
-    hipLaunchKernelGGL((base_value_bwd_wide<T, PR>), L.grid, L.block, L.lds, st, (const T*)dout, (const T*)x, wv,    \
-                       (const T*)dv, dyx, (T*)dx, dwv_part, (const T*)pre, pre_center, pre_tmom, B, C, H, W, L.BG, res, L.wc); \
-  }
-#define CALL(T) { if (pre_tmom) CALL_P(T, true) else CALL_P(T, false) }
-  switch (dtype) {
-    case MRLA_F32:  CALL(float) break;
-    case MRLA_BF16: CALL(bf16_t) break;
-    case MRLA_F16:  CALL(f16_t) break;
-    default: return MRLA_EINVAL;
-  }
-#undef CALL
-#undef CALL_P
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto sums) {
+    using T = typename decltype(t)::type;
+    const WideLaunch L = wide_launch(P_APPLY_BWD, B, C, W, 9, base_vbwd_wave_bytes<T, sums()>(), bg, false, nz);
+    return launch_kernel(base_value_bwd_wide<T, sums()>, L.grid, L.block, L.lds, st, dout, x, wv, dv, dyx, dx, dwv_part, pre,
+                         pre_center, pre_tmom, B, C, H, W, L.BG, res, L.wc);
+  }, pre_tmom != nullptr);
 }
 
 }  // namespace mrla

@@ -380,11 +380,6 @@ __global__ __launch_bounds__(kPoolWaves* kWave) void bn_relu_pool_bwd_kernel(con
   }
 }
 
-template <typename K>
-hipError_t pool_lds(K kernel, size_t bytes) {
-  return lds_opt_in(reinterpret_cast<const void*>(kernel), bytes);
-}
-
 constexpr int kPS = 4;
 
 struct PoolGeo {
@@ -422,29 +417,16 @@ int bn_pool_plan(int B, int C, int H, int W, int band, int* out) {
   return MRLA_OK;
 }
 
-#define MRLA_POOL_DISPATCH(DT, CALL)     \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 int launch_bn_relu_pool_fwd(const void* x, const float* sc, const float* sh, void* out, int B, int C, int H, int W,
                             int dtype, hipStream_t st) {
   if (!bn_pool_supported(B, C, H, W)) return MRLA_EUNSUPPORTED;
   const PoolGeo g = pool_geo(B, C, H, W, kPS);
   const dim3 grid(C / kWave, B * g.bands), block(g.nwaves * kWave);
-#define CALL(TT)                                                                                                     \
-  {                                                                                                                  \
-    const size_t lds = (size_t)g.nwaves * pool_fwd_wave_bytes<TT, kPS>();                                            \
-    if (pool_lds(bn_relu_pool_fwd_kernel<TT, kPS>, lds) != hipSuccess) return MRLA_EHIP;                             \
-    hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<TT, kPS>), grid, block, lds, st, (const TT*)x, sc, sh, (TT*)out, C, \
-                       H, W, g.Ho, g.Wo, g.bands);                                                                   \
-  }
-  MRLA_POOL_DISPATCH(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(bn_relu_pool_fwd_kernel<T, kPS>, grid, block, (size_t)g.nwaves * pool_fwd_wave_bytes<T, kPS>(), st,
+                         x, sc, sh, out, C, H, W, g.Ho, g.Wo, g.bands);
+  });
 }
 
 int launch_bn_relu_pool_dmoments(const void* dp, const void* x, const float* sc, const float* sh, const float* center,
@@ -452,16 +434,12 @@ int launch_bn_relu_pool_dmoments(const void* dp, const void* x, const float* sc,
   if (!bn_pool_supported(B, C, H, W)) return MRLA_EUNSUPPORTED;
   const PoolGeo g = pool_geo(B, C, H, W, kPS);
   const dim3 grid(C / kWave, B * g.bands), block(g.nwaves * kWave);
-#define CALL(TT)                                                                                                    \
-  {                                                                                                                 \
-    const size_t lds = (size_t)g.nwaves * (2 * kWave * sizeof(float) + pool_mom_wave_bytes<TT, kPS>());             \
-    if (pool_lds(bn_relu_pool_dmoments_kernel<TT, kPS>, lds) != hipSuccess) return MRLA_EHIP;                       \
-    hipLaunchKernelGGL((bn_relu_pool_dmoments_kernel<TT, kPS>), grid, block, lds, st, (const TT*)dp, (const TT*)x,  \
-                       sc, sh, center, tmom, C, H, W, g.Ho, g.Wo, g.bands);                                         \
-  }
-  MRLA_POOL_DISPATCH(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const size_t lds = (size_t)g.nwaves * (2 * kWave * sizeof(float) + pool_mom_wave_bytes<T, kPS>());
+    return launch_kernel(bn_relu_pool_dmoments_kernel<T, kPS>, grid, block, lds, st, dp, x, sc, sh, center, tmom, C, H, W,
+                         g.Ho, g.Wo, g.bands);
+  });
 }
 
 int launch_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, const float* sh, const float* cb, void* dx,
@@ -469,16 +447,11 @@ int launch_bn_relu_pool_bwd(const void* dp, const void* x, const float* sc, cons
   if (!bn_pool_supported(B, C, H, W)) return MRLA_EUNSUPPORTED;
   const PoolGeo g = pool_geo(B, C, H, W, kPS);
   const dim3 grid(C / kWave, B * g.bands), block(g.nwaves * kWave);
-#define CALL(TT)                                                                                                   \
-  {                                                                                                                \
-    const size_t lds = (size_t)g.nwaves * pool_bwd_wave_bytes<TT, kPS>();                                          \
-    if (pool_lds(bn_relu_pool_bwd_kernel<TT, kPS>, lds) != hipSuccess) return MRLA_EHIP;                           \
-    hipLaunchKernelGGL((bn_relu_pool_bwd_kernel<TT, kPS>), grid, block, lds, st, (const TT*)dp, (const TT*)x, sc,  \
-                       sh, cb, (TT*)dx, C, H, W, g.Ho, g.Wo, g.bands);                                             \
-  }
-  MRLA_POOL_DISPATCH(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(bn_relu_pool_bwd_kernel<T, kPS>, grid, block, (size_t)g.nwaves * pool_bwd_wave_bytes<T, kPS>(), st,
+                         dp, x, sc, sh, cb, dx, C, H, W, g.Ho, g.Wo, g.bands);
+  });
 }
 
 }  // namespace mrla

@@ -20,6 +20,7 @@
 
 #include "mrla_device.h"
 #include "mrla_kernels.h"
+#include "mrla_launch.h"
 
 namespace mrla {
 
@@ -428,22 +429,9 @@ __global__ __launch_bounds__(kThreads) void token_ln_bwd_kernel(
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#define MRLA_DISPATCH_TT(DT, CALL)       \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 // 16-channel chunks: the zero-padded fp32 map tiles are 16 KB each, so 4 (backward: two tiles) to 8 workgroups share a
 // CU; measured faster than 32-channel chunks (2-4 per CU) although a row of lanes then moves 64 instead of 128 bytes
 static int chunk_for(int C) { return C % 16 == 0 ? 16 : 0; }
-
-template <typename K>
-static hipError_t set_lds3(K kernel, size_t bytes) {
-  return lds_opt_in(reinterpret_cast<const void*>(kernel), bytes);
-}
 
 int launch_token_norm_pool(const void* x, const void* o, const float* wx, const float* bx, float eps, float* stats,
                            float* mom, int B, int n, int C, int dtype, hipStream_t st) {
@@ -453,18 +441,14 @@ int launch_token_norm_pool(const void* x, const void* o, const float* wx, const 
   const int vec = 16 / (int)dtype_size(dtype);
   const bool vec_ok = C % vec == 0 && C <= kWave * vec * kTokVecPasses &&
                       ((uintptr_t)x & 15) == 0 && (!o || ((uintptr_t)o & 15) == 0);
-#define CALL(TT)                                                                                                     \
-  if (vec_ok)                                                                                                        \
-    hipLaunchKernelGGL((token_stats_vec_kernel<TT>), dim3(wgs), dim3(kThreads), 0, st, (const TT*)x, (const TT*)o, eps, \
-                       stats, ntok, C);                                                                              \
-  else                                                                                                               \
-    hipLaunchKernelGGL((token_stats_kernel<TT>), dim3(wgs), dim3(kThreads), 0, st, (const TT*)x, (const TT*)o, eps, stats, \
-                       ntok, C);                                                                                     \
-  hipLaunchKernelGGL((token_pool_kernel<TT>), dim3((C + kWave - 1) / kWave, B), dim3(kThreads), 0, st, (const TT*)x, stats, \
-                     wx, bx, mom, n, C);
-  MRLA_DISPATCH_TT(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    const int rc = vec_ok ? launch_kernel(token_stats_vec_kernel<T>, dim3(wgs), dim3(kThreads), 0, st, x, o, eps, stats, ntok, C)
+                          : launch_kernel(token_stats_kernel<T>, dim3(wgs), dim3(kThreads), 0, st, x, o, eps, stats, ntok, C);
+    if (rc != MRLA_OK) return rc;
+    return launch_kernel(token_pool_kernel<T>, dim3((C + kWave - 1) / kWave, B), dim3(kThreads), 0, st, x, stats, wx, bx, mom,
+                         n, C);
+  });
 }
 
 int launch_token_apply_fwd(const void* x, const void* o, const float* stats, const float* wx, const float* bx,
@@ -477,15 +461,11 @@ int launch_token_apply_fwd(const void* x, const void* o, const float* stats, con
   const size_t lds = (size_t)(side + 2) * (side + 2) * CC * sizeof(float);
   if (lds > 150 * 1024) return MRLA_EUNSUPPORTED;
   const dim3 grid(C / CC, B);
-#define CALL(TT)                                                                                              \
-  {                                                                                                           \
-    if (set_lds3(token_apply_fwd_kernel<TT>, lds) != hipSuccess) return MRLA_EHIP;                              \
-    hipLaunchKernelGGL((token_apply_fwd_kernel<TT>), grid, dim3(kThreads), lds, st, (const TT*)x, (const TT*)o, \
-                       stats, wx, bx, wo, bo, wv, gate, lam, (TT*)out, n, C, side, d, CC, res);               \
-  }
-  MRLA_DISPATCH_TT(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_apply_fwd_kernel<T>, grid, dim3(kThreads), lds, st, x, o, stats, wx, bx, wo, bo, wv, gate, lam,
+                         out, n, C, side, d, CC, res);
+  });
 }
 
 int launch_token_apply_bwd(const void* dout, const void* x, const void* o, const float* stats, const float* wx,
@@ -499,16 +479,11 @@ int launch_token_apply_bwd(const void* dout, const void* x, const void* o, const
   const size_t lds = ((size_t)2 * (side + 2) * (side + 2) * CC + (size_t)kThreads * (Q_N + 1)) * sizeof(float);
   if (lds > 150 * 1024) return MRLA_EUNSUPPORTED;
   const dim3 grid(C / CC, B);
-#define CALL(TT)                                                                                              \
-  {                                                                                                           \
-    if (set_lds3(token_apply_bwd_kernel<TT>, lds) != hipSuccess) return MRLA_EHIP;                              \
-    hipLaunchKernelGGL((token_apply_bwd_kernel<TT>), grid, dim3(kThreads), lds, st, (const TT*)dout,           \
-                       (const TT*)x, (const TT*)o, stats, wx, bx, wo, bo, wv, gate, lam, dxn, part, bmom, n, C, \
-                       side, d, CC);                                                                          \
-  }
-  MRLA_DISPATCH_TT(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_apply_bwd_kernel<T>, grid, dim3(kThreads), lds, st, dout, x, o, stats, wx, bx, wo, bo, wv, gate,
+                         lam, dxn, part, bmom, n, C, side, d, CC);
+  });
 }
 
 int launch_token_ln_bwd(const void* dout, const void* x, const void* o, const float* dxn, const float* dyx,
@@ -516,12 +491,11 @@ int launch_token_ln_bwd(const void* dout, const void* x, const void* o, const fl
                         int n, int C, int res, int dtype, hipStream_t st) {
   const int ntok = B * n;
   const dim3 grid((ntok + kWaves - 1) / kWaves);
-#define CALL(TT)                                                                                              \
-  hipLaunchKernelGGL((token_ln_bwd_kernel<TT>), grid, dim3(kThreads), 0, st, (const TT*)dout, (const TT*)x,    \
-                     (const TT*)o, dxn, dyx, stats, wx, wo, lam, (TT*)dx, (TT*)dprev, ntok, n, C, res);
-  MRLA_DISPATCH_TT(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_ln_bwd_kernel<T>, grid, dim3(kThreads), 0, st, dout, x, o, dxn, dyx, stats, wx, wo, lam, dx,
+                         dprev, ntok, n, C, res);
+  });
 }
 
 }  // namespace mrla

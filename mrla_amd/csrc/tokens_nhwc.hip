@@ -457,14 +457,6 @@ __global__ __launch_bounds__(kMaxStrips * kWave) void token_fwd_rows(
 // ------------------------------------------------------------------------------------------------
 // launchers (C % 64 == 0)
 // ------------------------------------------------------------------------------------------------
-#define MRLA_DISPATCH_TN(DT, CALL)       \
-  switch (DT) {                          \
-    case MRLA_F32:  CALL(float); break;  \
-    case MRLA_BF16: CALL(bf16_t); break; \
-    case MRLA_F16:  CALL(f16_t); break;  \
-    default: return MRLA_EINVAL;         \
-  }
-
 bool token_nhwc_applies(int C) { return C % kWave == 0; }
 
 // Row bands of the forward apply kernel: a 14 x 14 map gives a wave only 14 dependent row steps and the grid only
@@ -486,16 +478,11 @@ int launch_token_apply_fwd_nhwc(const void* x, const void* o, const float* stats
                                 void* out, int B, int n, int C, int side, int d, int res, int dtype, hipStream_t st) {
   const int nwaves = std::min((side + kS - 1) / kS, kMaxStrips);
   const dim3 grid(C / kWave, B, token_bands(B, C, side)), block(nwaves * kWave);
-#define CALL(TT)                                                                                                    \
-  {                                                                                                                 \
-    const size_t lds = (size_t)nwaves * tok_fwd_wave_bytes<TT>();                                                   \
-    if (set_lds_n(token_fwd_rows<TT, false>, lds) != hipSuccess) return MRLA_EHIP;                                   \
-    hipLaunchKernelGGL((token_fwd_rows<TT, false>), grid, block, lds, st, (const TT*)x, (const TT*)o, stats, wx, bx, wo, \
-                       bo, wv, gate, lam, (TT*)out, n, C, side, d, res);                                            \
-  }
-  MRLA_DISPATCH_TN(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_fwd_rows<T, false>, grid, block, (size_t)nwaves * tok_fwd_wave_bytes<T>(), st, x, o, stats, wx,
+                         bx, wo, bo, wv, gate, lam, out, n, C, side, d, res);
+  });
 }
 
 int launch_token_apply_bwd_nhwc(const void* dout, const void* x, const void* o, const float* stats, const float* wx,
@@ -505,18 +492,12 @@ int launch_token_apply_bwd_nhwc(const void* dout, const void* x, const void* o, 
   const int nwaves = std::min((side + kS - 1) / kS, kMaxStrips);
   const dim3 grid(C / kWave, B), block(nwaves * kWave);
   const bool ragged = side % kS != 0;
-#define CALL_R(TT, RG)                                                                                             \
-  {                                                                                                                \
-    const size_t lds = (size_t)nwaves * (TQ_N + 1) * kWave * sizeof(float) + (size_t)nwaves * tok_bwd_wave_bytes<TT>(); \
-    if (set_lds_n(token_apply_bwd_rows<TT, RG, false>, lds) != hipSuccess) return MRLA_EHIP;                         \
-    hipLaunchKernelGGL((token_apply_bwd_rows<TT, RG, false>), grid, block, lds, st, (const TT*)dout, (const TT*)x,     \
-                       (const TT*)o, stats, wx, bx, wo, bo, wv, gate, lam, (const TT*)nullptr, dxn, part, bmom, n, C, side, d); \
-  }
-#define CALL(TT) { if (ragged) CALL_R(TT, true) else CALL_R(TT, false) }
-  MRLA_DISPATCH_TN(dtype, CALL)
-#undef CALL
-#undef CALL_R
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto rg) {
+    using T = typename decltype(t)::type;
+    const size_t lds = (size_t)nwaves * (TQ_N + 1) * kWave * sizeof(float) + (size_t)nwaves * tok_bwd_wave_bytes<T>();
+    return launch_kernel(token_apply_bwd_rows<T, rg(), false>, grid, block, lds, st, dout, x, o, stats, wx, bx, wo, bo, wv,
+                         gate, lam, nullptr, dxn, part, bmom, n, C, side, d);
+  }, ragged);
 }
 
 int launch_token_value_fwd_nhwc(const void* x, const float* stats, const float* wx, const float* bx, const float* wv,
@@ -524,28 +505,21 @@ int launch_token_value_fwd_nhwc(const void* x, const float* stats, const float* 
   if (!token_nhwc_applies(C)) return MRLA_EUNSUPPORTED;
   const int nwaves = std::min((side + kS - 1) / kS, kMaxStrips);
   const dim3 grid(C / kWave, B, token_bands(B, C, side)), block(nwaves * kWave);
-#define CALL(TT)                                                                                                    \
-  {                                                                                                                 \
-    const size_t lds = (size_t)nwaves * tok_fwd_wave_bytes<TT>();                                                   \
-    if (set_lds_n(token_fwd_rows<TT, true>, lds) != hipSuccess) return MRLA_EHIP;                                    \
-    hipLaunchKernelGGL((token_fwd_rows<TT, true>), grid, block, lds, st, (const TT*)x, (const TT*)nullptr, stats, wx, bx, \
-                       (const float*)nullptr, (const float*)nullptr, wv, (const float*)nullptr, (const float*)nullptr, \
-                       (TT*)vslot, n, C, side, 1, 0);                                                               \
-  }
-  MRLA_DISPATCH_TN(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_fwd_rows<T, true>, grid, block, (size_t)nwaves * tok_fwd_wave_bytes<T>(), st, x, nullptr, stats,
+                         wx, bx, nullptr, nullptr, wv, nullptr, nullptr, vslot, n, C, side, 1, 0);
+  });
 }
 
 // out[b, 0, :] = LN_x(x)[b, 0, :] (the cls token passes through the module, deit_mrla_base.py:241)
 int launch_token_cls_fwd(const void* x, const float* stats, const float* wx, const float* bx, void* out, int B, int n,
                          int C, int dtype, hipStream_t st) {
-#define CALL(TT)                                                                                                    \
-  hipLaunchKernelGGL((token_cls_fwd_kernel<TT>), dim3((C + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st,      \
-                     (const TT*)x, stats, wx, bx, (TT*)out, n, C, 0);
-  MRLA_DISPATCH_TN(dtype, CALL)
-#undef CALL
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return launch_kernel(token_cls_fwd_kernel<T>, dim3((C + kThreads - 1) / kThreads, B), dim3(kThreads), 0, st, x, stats, wx,
+                         bx, out, n, C, 0);
+  });
 }
 
 int launch_token_value_bwd_nhwc(const void* dout, const void* x, const float* stats, const float* wx, const float* bx,
@@ -555,19 +529,12 @@ int launch_token_value_bwd_nhwc(const void* dout, const void* x, const float* st
   const int nwaves = std::min((side + kS - 1) / kS, kMaxStrips);
   const dim3 grid(C / kWave, B), block(nwaves * kWave);
   const bool ragged = side % kS != 0;
-#define CALL_R(TT, RG)                                                                                             \
-  {                                                                                                                \
-    const size_t lds = (size_t)nwaves * (TQ_N + 1) * kWave * sizeof(float) + (size_t)nwaves * tok_bwd_wave_bytes<TT>(); \
-    if (set_lds_n(token_apply_bwd_rows<TT, RG, true>, lds) != hipSuccess) return MRLA_EHIP;                          \
-    hipLaunchKernelGGL((token_apply_bwd_rows<TT, RG, true>), grid, block, lds, st, (const TT*)dout, (const TT*)x,      \
-                       (const TT*)nullptr, stats, wx, bx, (const float*)nullptr, (const float*)nullptr, wv,        \
-                       (const float*)nullptr, (const float*)nullptr, (const TT*)dv, dxn, part, (float*)nullptr, n, C, side, 1); \
-  }
-#define CALL(TT) { if (ragged) CALL_R(TT, true) else CALL_R(TT, false) }
-  MRLA_DISPATCH_TN(dtype, CALL)
-#undef CALL
-#undef CALL_R
-  return hip_status(hipGetLastError());
+  return with_dtype(dtype, [&](auto t, auto rg) {
+    using T = typename decltype(t)::type;
+    const size_t lds = (size_t)nwaves * (TQ_N + 1) * kWave * sizeof(float) + (size_t)nwaves * tok_bwd_wave_bytes<T>();
+    return launch_kernel(token_apply_bwd_rows<T, rg(), true>, grid, block, lds, st, dout, x, nullptr, stats, wx, bx, nullptr,
+                         nullptr, wv, nullptr, nullptr, dv, dxn, part, nullptr, n, C, side, 1);
+  }, ragged);
 }
 
 }  // namespace mrla

@@ -11,6 +11,12 @@ SGPR, scratch, LDS and occupancy figures (from scripts/kernel_resources.py).  Ex
 
     python scripts/kernel_isa_diff.py /path/to/parent/checkout conv1x1.hip conv1x1_wide.hip
     python scripts/kernel_isa_diff.py /path/to/parent/checkout          # the five conv1x1 sources
+    python scripts/kernel_isa_diff.py /path/to/parent/checkout --all    # every source of the Makefile's SRC list
+
+A kernel that lost a template argument has another mangled name than the instance it came from: --map 'REGEX=REPL'
+(repeatable, re.sub on the PARENT's mangled names before the kernels are paired) names the pairing, e.g.
+--map 'Lb0EEEvPKT_=EEvPKT_' for a trailing `false` in front of a (const T*, ...) parameter list.  Two parent kernels that
+map to one name are an error.
 """
 import argparse
 import concurrent.futures
@@ -77,26 +83,47 @@ def figures(csrc, source, arch):
     return {k["mangled"].replace("12_GLOBAL__N_1", ""): k for k in kr.kernel_resources(source, arch, csrc=csrc)}
 
 
+def makefile_sources(csrc):
+    with open(os.path.join(csrc, "Makefile")) as f:
+        return next(l.split(":=", 1)[1].split() for l in f if re.match(r"SRC\s*:=", l))
+
+
+def renamed(kernels, maps):
+    """The parent's {mangled name: ...} under the --map expressions."""
+    out = {}
+    for name, value in kernels.items():
+        for pattern, repl in maps:
+            name = pattern.sub(repl, name)
+        if name in out:
+            raise SystemExit(f"--map gives two parent kernels the name {name}")
+        out[name] = value
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("parent", help="root of the checkout to compare against")
     ap.add_argument("sources", nargs="*", help=f"files of mrla_amd/csrc (default: {' '.join(CONV1X1)})")
+    ap.add_argument("--all", action="store_true", help="every source of this checkout's Makefile (its SRC list)")
+    ap.add_argument("--map", action="append", default=[], metavar="REGEX=REPL",
+                    help="re.sub applied to the parent's mangled names before kernels are paired (repeatable)")
     ap.add_argument("--tree", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."), help="this checkout")
     ap.add_argument("--arch", default="gfx950")
     ap.add_argument("-j", type=int, default=min(16, os.cpu_count() or 1))
     a = ap.parse_args()
-    sources = a.sources or CONV1X1
     trees = [csrc_of(a.parent), csrc_of(a.tree)]
+    sources = a.sources or (makefile_sources(trees[1]) if a.all else CONV1X1)
+    maps = [(re.compile(m.split("=", 1)[0]), m.split("=", 1)[1]) for m in a.map]
     jobs = [(t, s) for s in sources for t in trees]
     with concurrent.futures.ThreadPoolExecutor(a.j) as pool:
         asm = dict(zip(jobs, pool.map(lambda j: kernel_streams(assembly(*j, a.arch)), jobs)))
         res = dict(zip(jobs, pool.map(lambda j: figures(*j, a.arch), jobs)))
 
-    bad = 0
+    bad = total = 0
     print(f"{'file':22s} {'stream':9s} " + " ".join(f"{f:>11s}" for f in FIGURES) + "  kernel   (figures: parent/this)")
     for s in sources:
-        old, new = asm[(trees[0], s)], asm[(trees[1], s)]
-        ro, rn = res[(trees[0], s)], res[(trees[1], s)]
+        old, new = renamed(asm[(trees[0], s)], maps), asm[(trees[1], s)]
+        ro, rn = renamed(res[(trees[0], s)], maps), res[(trees[1], s)]
         names = kr.demangle(sorted(set(old) | set(new)))
         same = 0
         for name in sorted(set(old) | set(new)):
@@ -108,8 +135,9 @@ def main():
             bad += verdict != "same"
             cols = " ".join(f"{ro.get(name, {}).get(f, '-')!s:>5s}/{rn.get(name, {}).get(f, '-')!s:<5s}" for f in FIGURES)
             print(f"{s:22s} {verdict:9s} {cols}  {kr.short(names[name])}")
+        total += len(new)
         print(f"# {s}: {len(new)} kernels, {same} identical to the parent's", file=sys.stderr)
-    print(f"# {'all instruction streams identical' if not bad else str(bad) + ' kernels differ'}", file=sys.stderr)
+    print(f"# {total} kernels: {'all instruction streams identical' if not bad else str(bad) + ' differ'}", file=sys.stderr)
     return 1 if bad else 0
 
 

@@ -301,6 +301,50 @@ def test_wide_nchw_base_stage_goes_through_nhwc_rings():
         assert relmax(xts[t].grad.cpu().numpy(), grads[t]["dx"]) < ACT_TOL, t
 
 
+@pytest.mark.parametrize("shape", [(2, 48, 4, 15), (2, 16, 3, 5)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_value_backward_of_channel_counts_off_the_row_pipeline(shape, dtype):
+    """mrla_base_value_bwd_dv on channels_last tensors whose channel count is no multiple of 64: the pixel-by-pixel kernel
+    (base_value_bwd_nhwc), which BaseStage never picks (it keeps such stages NCHW), so it is called through the C ABI.  4 x 15:
+    three column strips, the last ragged, i.e. three waves whose dWv sums meet in the workgroup's LDS -- all the LDS the launch
+    asks for; 3 x 5: one wave, which leaves it untouched.  Reference: the formulas in fp64 on the same (rounded) inputs.  fp32: the file's
+    bounds.  bf16: dx is stored in bf16 (half an ulp = 2^-9 of the value, 2^-8 allowed), dWv is an fp32 sum of products that
+    are exact in fp32, so the fp32 parameter bound holds."""
+    from mrla_amd import _lib as L, functional as Fm
+    b, c, h, w = shape
+    s = detgen.seed_of(f"bvbwd/{c}/{w}")
+    rnd = bf16_round if dtype == torch.bfloat16 else (lambda a: np.asarray(a, np.float32))
+    x = rnd(np.maximum(detgen.normalish((b, h, w, c), s), 0))
+    dout, dv = rnd(detgen.normalish((b, h, w, c), s + 1)), rnd(detgen.normalish((b, h, w, c), s + 2))
+    wv = detgen.normalish((c, 3, 3), s + 3, 0.4).astype(np.float32)
+    dyx = detgen.normalish((b, c), s + 4, 0.1).astype(np.float32)
+    lib, dt = L.load(), Fm._DT[dtype]
+    rows = lib.mrla_light_wgrad_rows(b, c, h, w, dt, L.NHWC)
+    assert 1 <= rows <= b
+    xt, gt, vt = to_dev(x, dtype), to_dev(dout, dtype), to_dev(dv, dtype)
+    wt, yt = to_dev(wv), to_dev(dyx)
+    dx = torch.full_like(xt, float("nan"))
+    part = torch.full((rows, c, 9), float("nan"), device="cuda")
+    L.call("mrla_base_value_bwd_dv", Fm._ptr(gt), Fm._ptr(xt), Fm._ptr(wt), Fm._ptr(vt), Fm._ptr(yt), Fm._ptr(dx), Fm._ptr(part),
+           None, None, None, b, c, h, w, 3, dt, L.NHWC, Fm._stream())
+    torch.cuda.synchronize()
+    x64, v64 = x.astype(np.float64), np.pad(dv.astype(np.float64), ((0, 0), (1, 1), (1, 1), (0, 0)))
+    want = dout.astype(np.float64) + dyx.astype(np.float64)[:, None, None, :]
+    dwv = np.zeros((c, 3, 3))
+    for i in range(3):
+        for k in range(3):
+            shifted = v64[:, 2 - i:2 - i + h, 2 - k:2 - k + w, :]              # dV[r - i + 1][col - k + 1]
+            want += wv[:, i, k].astype(np.float64) * shifted
+            dwv[:, i, k] = (x64 * shifted).sum(axis=(0, 1, 2))
+    want *= x64 > 0
+    got = dx.float().cpu().numpy().astype(np.float64)
+    if dtype == torch.float32:
+        assert relmax(got, want) < ACT_TOL
+    else:
+        assert (np.abs(got - want) <= 2.0 ** -8 * np.abs(want) + 1e-5 * np.abs(want).max()).all()
+    assert relmax(part.sum(0).cpu().numpy().reshape(c, 3, 3), dwv) < par_tol("mrla.mrla.Wv.weight")
+
+
 @pytest.mark.parametrize("shape", [(3, 64, 6, 9), (4, 256, 14, 14), (2, 1024, 14, 14), (8, 128, 28, 28)],
                          ids=lambda s: "x".join(map(str, s)))
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])

@@ -49,3 +49,18 @@ def test_occupancy_the_planner_assumes(instances):
             continue                                   # never launched: conv1x1_geo() takes eight waves above K = 128
         need = 2 if nw == 8 else 3
         assert k["waves"] >= need, f"<{ks}, {mom}, {nw}>: {k['waves']} waves / SIMD ({k['vgprs']} VGPRs + {k['agprs']} AGPRs), needs {need}"
+
+
+def test_isa_diff_pairs_renamed_kernels_and_reads_the_makefile():
+    """scripts/kernel_isa_diff.py: --all takes the Makefile's SRC list, and --map renames the parent's mangled names before the
+    kernels are paired (a kernel that lost a template argument meets the instance it came from); two parent kernels under
+    one name are an error, not a silent pairing."""
+    import kernel_isa_diff as kd
+    sources = kd.makefile_sources(os.path.join(ROOT, "mrla_amd", "csrc"))
+    assert "light_nhwc_wide.hip" in sources and "capi.hip" in sources and len(sources) == len(set(sources))
+    assert all(os.path.exists(os.path.join(ROOT, "mrla_amd", "csrc", s)) for s in sources)
+    maps = [(re.compile(r"(kernelI\w+?)Lb0EEEv"), r"\1EEv")]
+    parent = {"_ZN4mrla6kernelIfLb1ELb0EEEvPKT_": 1, "_ZN4mrla5otherIfEEvPKT_": 2}
+    assert kd.renamed(parent, maps) == {"_ZN4mrla6kernelIfLb1EEEvPKT_": 1, "_ZN4mrla5otherIfEEvPKT_": 2}
+    with pytest.raises(SystemExit):
+        kd.renamed({"_ZN4mrla6kernelIfLb0EEEvPKT_": 1, "_ZN4mrla6kernelIfEEvPKT_": 2}, maps)
