@@ -763,6 +763,29 @@ int mrla_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y, 
 int mrla_conv1x1_f32_wgrad_rows(int m, int k, int n);
 int mrla_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int m, int k, int n, void* stream);
 
+/* The weight gradient of the 3x3 convolution (padding 1, dilation 1, groups 1, stride 1 or 2) for the same fp32 recipe: three
+ * ADDITIVE symbols, MRLA_ABI_VERSION stays 5, and mrla_conv3x3_wgrad* above go on refusing MRLA_F32.
+ *     dw[n, kh, kw, c] = sum_{b, y, x} dy[b, y, x, n] * x[b, y*stride + kh - 1, x*stride + kw - 1, c]
+ *   x: [b, h, w, c] and dy: [b, ho, wo, n] channels_last fp32 activations, ho = (h-1)/stride + 1, wo = (w-1)/stride + 1; taps
+ *   outside an image contribute nothing; dw: [n, 3, 3, c] fp32 -- a [n, c, 3, 3] tensor in channels_last memory format;
+ *   part: fp32 workspace [rows, n, 9, c] with rows = mrla_conv3x3_f32_wgrad_rows(...): the per-workgroup partial tiles of the
+ *   fixed split over output rows, summed in ascending order by a second kernel.
+ * Every product is a fused multiply-add on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32), each partial sum one chain in
+ * a fixed order.  No atomics and no memset: every element of part and dw is written exactly once per call, nothing is read
+ * outside x and dy, and the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from
+ * a replayed graph.
+ * MRLA_EUNSUPPORTED unless c % 64 == 0, n % 64 == 0, stride is 1 or 2 and b * h * w * max(c, n) * 4 < 2^31; any b, h, w >= 1
+ * within that (odd sizes, maps smaller than the kernel, rows wider than one step).  MRLA_EINVAL, decided on the host before
+ * anything is launched: a non-positive dimension or stride, a NULL pointer (`out` included), a pointer that is not 16-byte
+ * aligned.  The queries answer the same code as the launch for the same arguments.
+ * mrla_conv3x3_f32_wgrad_plan: `out` is a HOST array of 6 ints: tile n, tile c, output rows (image rows of dy, numbered image
+ * after image) per split, LDS stages, splits (= mrla_conv3x3_f32_wgrad_rows()), output tiles.  Split i takes the rows
+ * [i * out[2], min(b * ho, (i + 1) * out[2])).  There is no `_preferred` query: nothing routes fp32 by shape. */
+int mrla_conv3x3_f32_wgrad_rows(int b, int c, int n, int h, int w, int stride);      /* rows of part (> 0), or a negative code */
+int mrla_conv3x3_f32_wgrad_plan(int b, int c, int n, int h, int w, int stride, int* out);
+int mrla_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int c, int n, int h, int w,
+                           int stride, void* stream);
+
 /* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input
  * gradient): replaces what torch.autocast does in front of nn.Conv2d (resnet/train.py runs fp32; the bf16 configuration of

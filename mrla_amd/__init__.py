@@ -19,6 +19,9 @@ def __getattr__(name):
     if name == "conv3x3_wgrad_auto":   # ... and of its route by shape, where the library prefers it (functional.CONV3X3_WGRAD_AUTO)
         from . import functional
         return functional.conv3x3_wgrad_auto
+    if name == "conv3x3_wgrad_f32":    # ... and of the fp32 3x3 weight gradient outside autocast (functional.CONV3X3_WGRAD_F32)
+        from . import functional
+        return functional.conv3x3_wgrad_f32
     if name == "conv3x3_fwd":    # the switch of the own 3x3 forward and stride-1 input gradient (functional.CONV3X3_FWD)
         from . import functional
         return functional.conv3x3_fwd
@@ -28,7 +31,7 @@ def __getattr__(name):
     if name == "stem_wgrad":      # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
         from . import functional
         return functional.stem_wgrad
-    if name == "reproducible_gradients":      # both of them: every parameter gradient a function of the step's inputs alone
+    if name == "reproducible_gradients":      # all of them (the fp32 3x3 one included): every parameter gradient a function of the step's inputs alone
         from . import functional
         return functional.reproducible_gradients
     raise AttributeError(f"module 'mrla_amd' has no attribute {name!r}")

@@ -109,6 +109,9 @@ SIGNATURES = {
     "mrla_conv1x1_f32_fwd": [_P, _P, _I, _P, _P, _I, _I, _I, _P],
     "mrla_conv1x1_f32_wgrad_rows": [_I] * 3,
     "mrla_conv1x1_f32_wgrad": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "mrla_conv3x3_f32_wgrad_rows": [_I] * 6,
+    "mrla_conv3x3_f32_wgrad_plan": [_I] * 6 + [_P],
+    "mrla_conv3x3_f32_wgrad": [_P, _P, _P, _P] + [_I] * 6 + [_P],
     "mrla_conv1x1_wgrad_bn_supported": [_I] * 4,
     "mrla_conv1x1_wgrad_bn": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "mrla_conv1x1_wgrad_bn_dx_supported": [_I] * 4,
@@ -208,6 +211,11 @@ def conv1x1_wgrad_plan(m, k, n, dtype=None):
 def conv3x3_wgrad_plan(b, c, n, h, w, stride, dtype=None):
     """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_wgrad, or None."""
     return _plan("mrla_conv3x3_wgrad_plan", 6, b, c, n, h, w, stride, dtype)
+
+
+def conv3x3_f32_wgrad_plan(b, c, n, h, w, stride):
+    """(tile n, tile c, output rows per split, LDS stages, splits, tiles) of mrla_conv3x3_f32_wgrad, or None."""
+    return _plan("mrla_conv3x3_f32_wgrad_plan", 6, b, c, n, h, w, stride)
 
 
 def conv3x3_fwd_plan(b, c, n, h, w, stride, dtype=None):

@@ -901,6 +901,33 @@ int mrla_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* 
   return launch_conv1x1_f32_wgrad(dy, x, part, dw, m, k, n, (hipStream_t)stream);
 }
 
+// The fp32 3x3 weight gradient (conv3x3_wgrad_f32.hip): symbols of its own -- mrla_conv3x3_wgrad* go on refusing MRLA_F32.  One
+// argument check for the queries and the launch, so that they answer the same code for the same arguments.
+static int conv3x3_f32_args(int b, int c, int n, int h, int w, int stride) {
+  return (b <= 0 || c <= 0 || n <= 0 || h <= 0 || w <= 0 || stride <= 0) ? MRLA_EINVAL : MRLA_OK;
+}
+
+int mrla_conv3x3_f32_wgrad_rows(int b, int c, int n, int h, int w, int stride) {
+  const int rc = conv3x3_f32_args(b, c, n, h, w, stride);
+  return rc != MRLA_OK ? rc : conv3x3_f32_wgrad_rows(b, c, n, h, w, stride);
+}
+
+int mrla_conv3x3_f32_wgrad_plan(int b, int c, int n, int h, int w, int stride, int* out) {
+  if (!out) return MRLA_EINVAL;
+  const int rc = conv3x3_f32_args(b, c, n, h, w, stride);
+  return rc != MRLA_OK ? rc : conv3x3_f32_wgrad_plan(b, c, n, h, w, stride, out);
+}
+
+int mrla_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int c, int n, int h, int w,
+                           int stride, void* stream) {
+  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
+  // a lane moves 16 bytes of dy, x and part, and four elements of dw
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
+  const int rc = conv3x3_f32_args(b, c, n, h, w, stride);
+  if (rc != MRLA_OK) return rc;
+  return launch_conv3x3_f32_wgrad(dy, x, part, dw, b, c, n, h, w, stride, (hipStream_t)stream);
+}
+
 int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype) {
   const int rc = conv1x1_args(m, k, n, dtype);
   return rc != MRLA_OK ? rc : conv1x1_wgrad_bn_supported(m, k, n);

@@ -257,6 +257,12 @@ int launch_conv1x1_f32_fwd(const float* x, const float* w, int w_trans, float* y
                            hipStream_t st);
 int conv1x1_f32_wgrad_rows(int M, int K, int N);
 int launch_conv1x1_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int M, int K, int N, hipStream_t st);
+// conv3x3_wgrad_f32.hip -- the weight gradient of a 3x3 / padding 1 / stride s (1 or 2) convolution of fp32 operands on that
+// MFMA, dW [n,3,3,c] fp32; part [rows][n][9][c]
+int conv3x3_f32_wgrad_rows(int b, int c, int n, int h, int w, int s);
+int conv3x3_f32_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
+int launch_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int c, int n, int h, int w, int s,
+                             hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)

@@ -124,6 +124,21 @@ CONV3X3_WGRAD_AUTO = True   # the same route by shape: an eligible 3x3 convoluti
 conv3x3_wgrad_auto = _switch("CONV3X3_WGRAD_AUTO", "conv3x3_wgrad_auto")
 
 
+CONV3X3_WGRAD_F32 = False   # the weight gradient of an eligible fp32 3x3 convolution outside autocast (conv3x3_f32_applies: the
+#                             recipe of resnet/train.py:397-409) comes from mrla_conv3x3_f32_wgrad -- the fixed split and
+#                             summation order of mrla_conv3x3_wgrad on the exact fp32-input MFMA, no atomics: a function of
+#                             its arguments, eagerly and from a replayed graph, where the stock library's find mode picks an
+#                             fp32 split-K solver that accumulates with atomics into a zero-filled buffer.  Forward
+#                             and input gradient stay the stock operator's.  False (the default): conv(x) itself, the very
+#                             same autograd graph and launches as before; conv3x3_wgrad_f32() turns it on for a block of
+#                             code, reproducible_gradients() together with the 16-bit switches.  CONV3X3_WGRAD and
+#                             CONV3X3_WGRAD_AUTO never route fp32.  Nothing is routed by shape: profiles/conv3x3_wgrad_f32.md
+#                             has the numbers a default would rest on.
+
+
+conv3x3_wgrad_f32 = _switch("CONV3X3_WGRAD_F32", "conv3x3_wgrad_f32")
+
+
 CONV3X3_FWD = False   # the forward of an eligible 3x3 convolution (conv3x3_fwd_applies: the bottleneck's conv2, both of the basic
 #                       block's; inference and frozen stages included) comes from mrla_conv3x3_fwd -- one fixed summation order,
 #                       no split of the reduction: a function of its inputs alone, where the stock operator's output differs
@@ -164,9 +179,11 @@ stem_wgrad = _switch("STEM_WGRAD", "stem_wgrad")
 
 @contextlib.contextmanager
 def reproducible_gradients(enabled=True):
-    """CONV3X3_WGRAD and STEM_WGRAD = `enabled` inside the block: with both on no weight gradient of a resnet*_mrlal step is
-    left to an atomic split-K solver.  The previous values come back on exit, also when the block raises."""
-    with conv3x3_wgrad(enabled), stem_wgrad(enabled):
+    """CONV3X3_WGRAD, CONV3X3_WGRAD_F32 and STEM_WGRAD = `enabled` inside the block: with them on no weight gradient of a
+    bf16 or fp16 resnet*_mrlal step is left to an atomic split-K solver, and in an fp32 step (no autocast) none of a 3x3
+    convolution.  In fp32 the stem's 7x7 gradient is still the stock operator's: there is no fp32 stem kernel.  The previous
+    values come back on exit, also when the block raises."""
+    with conv3x3_wgrad(enabled), conv3x3_wgrad_f32(enabled), stem_wgrad(enabled):
         yield
 
 
@@ -2058,11 +2075,12 @@ def _conv_compute_dtype(x):
     return x.dtype
 
 
-def _spatial_conv_applies(conv, x, kernel, strides, padding, want_wgrad):
+def _spatial_conv_applies(conv, x, kernel, strides, padding, want_wgrad, dtypes=(torch.bfloat16, torch.float16)):
     """The compute dtype where `conv(x)` is a convolution the own spatial kernels take, else None: a bias-free nn.Conv2d of
     this kernel size and padding, one of `strides`, dilation 1, groups 1, zero padding; a CUDA channels_last 16-byte-aligned
     input of conv's channels that the convolution computes in bf16 or fp16 (its own dtype, or autocast's) on a CUDA weight
-    of that dtype (as stored, or as autocast casts it); with `want_wgrad`, grad mode and a weight that wants its gradient."""
+    of that dtype (as stored, or as autocast casts it); with `want_wgrad`, grad mode and a weight that wants its gradient.
+    `dtypes`: the compute dtypes taken instead of bf16 and fp16."""
     if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == kernel and conv.stride in strides and conv.padding == padding
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"):
         return None
@@ -2074,7 +2092,7 @@ def _spatial_conv_applies(conv, x, kernel, strides, padding, want_wgrad):
     if not (wt.is_cuda and x.shape[1] == conv.in_channels):
         return None
     dt, auto = _conv_compute_dtype(x), torch.is_autocast_enabled("cuda")
-    if dt not in (torch.bfloat16, torch.float16) or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
+    if dt not in dtypes or not (x.dtype == dt or (auto and x.dtype == torch.float32)):
         return None
     if not (wt.dtype == dt or (auto and wt.dtype == torch.float32)):       # (the weight as stored, or as autocast casts it)
         return None
@@ -2084,16 +2102,16 @@ def _spatial_conv_applies(conv, x, kernel, strides, padding, want_wgrad):
 def _own_wgrad(ctx, entry, rows_entry, dy, x, shape, taps):
     """The weight gradient [n, *taps] of a spatial convolution from its own entry point, in the weight's own dtype and laid
     out as a channels_last [n, c, kh, kw]; None where the kernel does not take the shape (`shape`: the entry point's
-    integers in front of the dtype)."""
-    dt = _DT[x.dtype]
-    rows = getattr(L.load(), rows_entry)(*shape, dt)
+    integers in front of the dtype).  The fp32 entry point (an fp32 `x`: _OWN_WGRAD_F32) takes no dtype codes."""
+    codes = () if x.dtype == torch.float32 else (_DT[x.dtype], _DT[ctx.wdtype])
+    rows = getattr(L.load(), rows_entry)(*shape, *codes[:1])
     if rows <= 0:
         return None
     n, (kh, kw, c) = dy.shape[1], taps
     part = torch.empty((rows, n, kh * kw * c), dtype=torch.float32, device=x.device)
     gw = torch.empty((n, c, kh, kw), dtype=ctx.wdtype, device=x.device, memory_format=_CL)
-    _call(entry, (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), *shape, dt,
-          _DT[ctx.wdtype], _stream())
+    _call(entry, (dy.numel() + x.numel()) * x.element_size(), _ptr(dy), _ptr(x), _ptr(part), _ptr(gw), *shape, *codes,
+          _stream())
     return gw
 
 
@@ -2118,12 +2136,13 @@ def _weight_strides(ctx, gw):
 
 
 _OWN_WGRAD = {3: ("mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows"), 7: ("mrla_stem_conv_wgrad", "mrla_stem_conv_wgrad_rows")}
+_OWN_WGRAD_F32 = {3: ("mrla_conv3x3_f32_wgrad", "mrla_conv3x3_f32_wgrad_rows")}      # an fp32 x and an fp32 weight
 
 
 def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=False):
     """(gx, gw) of a spatial convolution node that saved (x, working weight) and noted ctx.stride: the weight gradient from
-    the own kernel if `own_wgrad`; the input gradient from the own forward on the flipped, transposed weight (a pure
-    permutation) if `flipped_dgrad` at stride 1, from mrla_conv3x3_dgrad_s2 if `own_dgrad` -- each only for a gradient of x's
+    the own kernel if `own_wgrad` (the entry point by x's dtype); the input gradient from the own forward on the flipped,
+    transposed weight (a pure permutation) if `flipped_dgrad` at stride 1, from mrla_conv3x3_dgrad_s2 if `own_dgrad` -- each only for a gradient of x's
     dtype at a 16-byte-aligned address; whatever is asked for and still missing from the stock backward, masked to exactly
     that; the weight gradient in the weight's own dtype and strides (autograd's / DDP's layout contract)."""
     x, w16 = ctx.saved_tensors
@@ -2133,9 +2152,10 @@ def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=Fa
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     own = dy.dtype == x.dtype and dy.data_ptr() % 16 == 0
     gx = gw = None
-    if need_w and own and own_wgrad:
+    entries = _OWN_WGRAD_F32 if x.dtype == torch.float32 else _OWN_WGRAD
+    if need_w and own and own_wgrad and k in entries:
         shape = (b, c, n, h, wd, ctx.stride[0]) if k == 3 else (b, n, h, wd)
-        gw = _own_wgrad(ctx, *_OWN_WGRAD[k], dy, x, shape, (k, k, c))
+        gw = _own_wgrad(ctx, *entries[k], dy, x, shape, (k, k, c))
     if need_x and own and flipped_dgrad and ctx.stride[0] == 1:
         wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
         gx = torch.empty_like(x)
@@ -2162,6 +2182,19 @@ def conv3x3_applies(conv, x):
         return False
     b, c, h, w = x.shape
     return L.load().mrla_conv3x3_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0], _DT[dt]) > 0
+
+
+def conv3x3_f32_applies(conv, x):
+    """True when the weight gradient of `conv(x)` belongs on mrla_conv3x3_f32_wgrad: the module conditions of conv3x3_applies
+    (a bias-free nn.Conv2d 3x3 / padding 1 / dilation 1 / groups 1 / stride (1, 1) or (2, 2), zero padding), grad mode and an
+    fp32 CUDA weight that wants its gradient, a CUDA channels_last 16-byte-aligned fp32 input that the convolution computes
+    in fp32 (no autocast), and a shape the kernel takes (mrla_conv3x3_f32_wgrad_rows).  conv3x3_applies goes on answering
+    False for all of these."""
+    dt = _spatial_conv_applies(conv, x, (3, 3), ((1, 1), (2, 2)), (1, 1), True, dtypes=(torch.float32,))
+    if dt is None or x.dtype != torch.float32 or conv.weight.dtype != torch.float32:
+        return False
+    b, c, h, w = x.shape
+    return L.load().mrla_conv3x3_f32_wgrad_rows(b, c, conv.out_channels, h, w, conv.stride[0]) > 0
 
 
 _WGRAD_PREFERRED = {}      # (b, c, n, h, w, stride, dtype code) -> mrla_conv3x3_wgrad_preferred(...) == 1
@@ -2198,7 +2231,8 @@ class _Conv3x3Fn(torch.autograd.Function):
     at the call), in the weight's own dtype -- for an fp32 master weight the fp32 sums themselves, no 16-bit rounding and no
     cast kernel -- returned as [n, c, 3, 3]; dX from mrla_conv3x3_dgrad_s2 where `own_dgrad` (CONV3X3_DGRAD and
     conv3x3_dgrad_applies at the call); what is left from the stock operator's backward, masked to exactly that (its split-K
-    weight-gradient solver is never invoked under `own_wgrad`)."""
+    weight-gradient solver is never invoked under `own_wgrad`).  An fp32 `x` with an fp32 `w` (CONV3X3_WGRAD_F32 and
+    conv3x3_f32_applies at the call) is the same node: dW then comes from mrla_conv3x3_f32_wgrad."""
 
     @staticmethod
     @_on_device
@@ -2285,12 +2319,13 @@ def conv3x3(x, conv):
     """conv(x) for the 3x3 convolutions of the blocks (resnet_mrla_light.py: conv2 of the bottleneck, both of the basic
     block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, where
     neither the own weight gradient (conv3x3_applies, and CONV3X3_WGRAD or CONV3X3_WGRAD_AUTO at a shape
-    mrla_conv3x3_wgrad_preferred answers 1 for) nor CONV3X3_DGRAD with conv3x3_dgrad_applies holds, it IS conv(x): the same
-    autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn) whose forward is the stock operator's, whose weight
-    gradient is mrla_conv3x3_wgrad's under the first and whose input gradient is mrla_conv3x3_dgrad_s2's under the second."""
+    mrla_conv3x3_wgrad_preferred answers 1 for; in fp32 conv3x3_f32_applies and CONV3X3_WGRAD_F32) nor CONV3X3_DGRAD with
+    conv3x3_dgrad_applies holds, it IS conv(x): the same autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn)
+    whose forward is the stock operator's, whose weight gradient is mrla_conv3x3_wgrad's (fp32: mrla_conv3x3_f32_wgrad's)
+    under the first and whose input gradient is mrla_conv3x3_dgrad_s2's under the second."""
     if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
         return _conv3x3_own(x, conv, False)[0]
-    own_wgrad = _conv3x3_own_wgrad(conv, x)
+    own_wgrad = _conv3x3_own_wgrad(conv, x) or (CONV3X3_WGRAD_F32 and conv3x3_f32_applies(conv, x))
     own_dgrad = CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x)
     if not (own_wgrad or own_dgrad):
         return conv(x)
