@@ -79,7 +79,9 @@ enum { MRLA_BN_NONE = 0, MRLA_BN_TRAIN = 1, MRLA_BN_EVAL = 2 };
  *           same answers for the same (m, k, n) -- callers that pass MRLA_BF16 see no change -- and
  *           mrla_weight_bank_refresh_dt was added beside mrla_weight_bank_refresh;  mrla_bn_pool_plan was added;
  *           the five mrla_conv1x1_f32_* symbols (fp32 operands on the fp32-input MFMA) were added -- every mrla_conv1x1_*
- *           entry point that takes a dtype goes on answering MRLA_EUNSUPPORTED for MRLA_F32.
+ *           entry point that takes a dtype goes on answering MRLA_EUNSUPPORTED for MRLA_F32;
+ *           mrla_conv3x3_weight_bank_refresh and mrla_conv3x3_dgrad_flip_preferred were added (the stride-1 3x3 input
+ *           gradient as a forward convolution on banked flipped weights) -- nothing above them changes.
  * A consumer compares mrla_abi_version() (what the loaded library was built from) against this constant before its
  * first call. */
 #define MRLA_ABI_VERSION 5
@@ -658,6 +660,14 @@ int mrla_conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int stride, int d
 int mrla_conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int stride, int dtype);
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w,
                        int stride, int dtype, int dw_dtype, void* stream);
+/* Host-side query (one more ADDITIVE symbol, MRLA_ABI_VERSION stays 5), for STRIDE 1 only: 1 where the input gradient of that
+ * convolution is expected to take less device time on MI355X as the stock forward convolution of dy with the flipped,
+ * transposed weight -- dx = conv(dy, wflip), wflip[c, n, kh, kw] = w[n, c, 2 - kh, 2 - kw], which
+ * mrla_conv3x3_weight_bank_refresh keeps -- than as the stock backward-data solver and the zero-fill of dx in front of it;
+ * else 0; the negative codes of mrla_conv3x3_wgrad_rows for the arguments it refuses.  A rule in the problem's quantities
+ * (c == n, the multiply-adds b * h * w * 9 * c * n of the launch), not a list of shapes; its derivation from measurements
+ * is profiles/conv3x3_dgrad_flip.md section 1.  MRLA_BF16 only was measured: 0 for MRLA_F16. */
+int mrla_conv3x3_dgrad_flip_preferred(int b, int c, int n, int h, int w, int dtype);
 
 /* Forward of that 3x3 convolution, padding 1, dilation 1, groups 1, stride `stride` = 1 or 2 in both directions, as an implicit
  * GEMM on the MFMA with the BatchNorm moment records of its outputs (three ADDITIVE symbols, MRLA_ABI_VERSION stays 5) --
@@ -797,6 +807,19 @@ int mrla_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* 
  * MRLA_BF16 or MRLA_F16 (round to nearest even, overflow to +-inf, as a torch cast), MRLA_EUNSUPPORTED for MRLA_F32. */
 int mrla_weight_bank_refresh(const void* table, int entries, int max_tiles, void* stream);
 int mrla_weight_bank_refresh_dt(const void* table, int entries, int max_tiles, int dtype, void* stream);
+/* The same for the fp32 3x3 weights [n, c, 3, 3] whose stride-1 input gradient runs as a forward convolution (additive,
+ * ABI 5): per weight the copy the forward multiplies with and the flipped, transposed copy the input gradient multiplies
+ * with, all weights in ONE launch -- instead of one autocast cast kernel per convolution and forward and two permuting
+ * copies per input gradient.
+ *   table: DEVICE array of `entries` x 5 int64: { src fp32 pointer, w16 pointer, wflip pointer, (n << 32) | c, src_cl };
+ *          src_cl != 0: src is [n][3][3][c] in memory (a channels_last [n, c, 3, 3]), else [n][c][3][3];  src 16-byte,
+ *          w16 and wflip 8-byte aligned;  n % 64 == 0, c % 64 == 0.
+ *          w16[n][kh][kw][c] = T(src[n, c, kh, kw])         -- a channels_last [n, c, 3, 3]
+ *          wflip[c][2-kh][2-kw][n] = the same 16 bits        -- a channels_last [c, n, 3, 3]
+ *   max_tiles: the largest 9 * (n / 64) * (c / 64) over the entries.
+ * dtype MRLA_BF16 or MRLA_F16 (round to nearest even, overflow to +-inf, as a torch cast), MRLA_EUNSUPPORTED for MRLA_F32;
+ * MRLA_EINVAL for a NULL table, entries <= 0, max_tiles <= 0 or a dtype code that is none. */
+int mrla_conv3x3_weight_bank_refresh(const void* table, int entries, int max_tiles, int dtype, void* stream);
 
 /* out[n] = sum over rows of in[rows, n] (fixed order, double accumulation). */
 int mrla_reduce_rows(const float* in, float* out, int rows, int n, void* stream);

@@ -28,6 +28,9 @@ def __getattr__(name):
     if name == "conv3x3_dgrad":    # the switch of the own stride-2 3x3 input gradient (functional.CONV3X3_DGRAD)
         from . import functional
         return functional.conv3x3_dgrad
+    if name == "conv3x3_dgrad_flip":   # the switch of the stride-1 3x3 input gradient as a stock forward on banked flipped weights
+        from . import functional       # (functional.CONV3X3_DGRAD_FLIP)
+        return functional.conv3x3_dgrad_flip
     if name == "stem_wgrad":      # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
         from . import functional
         return functional.stem_wgrad

@@ -119,6 +119,7 @@ SIGNATURES = {
     "mrla_conv3x3_wgrad_rows": [_I] * 7,
     "mrla_conv3x3_wgrad_plan": [_I] * 7 + [_P],
     "mrla_conv3x3_wgrad_preferred": [_I] * 7,
+    "mrla_conv3x3_dgrad_flip_preferred": [_I] * 6,
     "mrla_conv3x3_wgrad": [_P, _P, _P, _P] + [_I] * 8 + [_P],
     "mrla_conv3x3_fwd_rows": [_I] * 7,
     "mrla_conv3x3_fwd_plan": [_I] * 7 + [_P],
@@ -130,6 +131,7 @@ SIGNATURES = {
     "mrla_stem_conv_wgrad": [_P, _P, _P, _P] + [_I] * 6 + [_P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],
     "mrla_weight_bank_refresh_dt": [_P, _I, _I, _I, _P],
+    "mrla_conv3x3_weight_bank_refresh": [_P, _I, _I, _I, _P],
     "mrla_reduce_rows": [_P, _P, _I, _I, _P],
     "mrla_reduce_rows2": [_P, _P, _I, _I, _P, _P, _I, _I, _P],
     # sequence entry points (ABI 4): one call = the static launch sequence of a tail and direction

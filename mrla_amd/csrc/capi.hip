@@ -810,6 +810,12 @@ int mrla_conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int stride, 
   return rc != MRLA_OK ? rc : conv3x3_wgrad_preferred(b, c, n, h, w, stride);
 }
 
+int mrla_conv3x3_dgrad_flip_preferred(int b, int c, int n, int h, int w, int dtype) {
+  const int rc = conv3x3_args(b, c, n, h, w, 1, dtype);
+  if (rc != MRLA_OK) return rc;
+  return dtype == MRLA_BF16 && conv3x3_dgrad_flip_preferred(b, c, n, h, w);      // (fp16 was not measured)
+}
+
 int mrla_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int b, int c, int n, int h, int w, int stride,
                        int dtype, int dw_dtype, void* stream) {
   const int rc = wgrad_launch_args(dy, x, part, dw, dtype, dw_dtype, conv3x3_args(b, c, n, h, w, stride, dtype));
@@ -973,6 +979,12 @@ int mrla_weight_bank_refresh_dt(const void* table, int entries, int max_tiles, i
   if (!table || entries <= 0 || max_tiles <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
   if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
   return launch_weight_bank_refresh((const long long*)table, entries, max_tiles, dtype, (hipStream_t)stream);
+}
+
+int mrla_conv3x3_weight_bank_refresh(const void* table, int entries, int max_tiles, int dtype, void* stream) {
+  if (!table || entries <= 0 || max_tiles <= 0 || bad_dtype(dtype)) return MRLA_EINVAL;
+  if (dtype != MRLA_BF16 && dtype != MRLA_F16) return MRLA_EUNSUPPORTED;
+  return launch_conv3x3_weight_bank_refresh((const long long*)table, entries, max_tiles, dtype, (hipStream_t)stream);
 }
 
 int mrla_reduce_rows(const float* in, float* out, int rows, int n, void* stream) {

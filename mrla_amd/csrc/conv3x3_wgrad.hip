@@ -315,6 +315,23 @@ int conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int s) {
   return s == 1 && steps >= kC3PreferSteps && pixels >= kC3PreferPixels;
 }
 
+// 1 where the stride-1 input gradient is expected to take less device time as the stock FORWARD convolution of dy with the
+// flipped, transposed weight (mrla_conv3x3_weight_bank_refresh keeps that weight) than as the stock backward-data solver with
+// the zero-fill of dX in front of it.  profiles/conv3x3_dgrad_flip.md section 1: the forward solver wins by 9 - 35 us a launch
+// once the launch has work enough -- in the plan's quantities the multiply-adds b * h * w * 9 * c * n, the same number for
+// every stage of a ResNet at one batch -- and the zero-fill it saves grows with the bytes of dX; what the route costs is a
+// share (1.1 us) of one refresh launch.  Measured with c == n only (every stride-1 3x3 convolution of the networks), where the
+// forward problem is the layer's own forward and the stock library has its solver chosen already: nothing else is routed.
+// kFlipMinMacs is the class of 224 x 224 images at batch 96: from there on every width won by more than twice the run-to-run
+// spread at every measured batch (96, 128, 256).  Batch 64 won as well and batch 32 at three widths of four (512 channels on
+// 7 x 7 lost by 1.8 us); they stay with the stock gradient, as do the two-image detection shapes (5e9 multiply-adds, won by
+// 7 - 15 us), which a rule in this one quantity cannot tell from a batch-43 step.
+constexpr long long kFlipMinMacs = 96LL * 56 * 56 * 9 * 64 * 64;
+int conv3x3_dgrad_flip_preferred(int b, int c, int n, int h, int w) {
+  if (c != n || c % 64) return 0;
+  return (double)b * h * w * 9.0 * c * n >= (double)kFlipMinMacs;       // (double: no overflow for any int arguments)
+}
+
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
                          int s, int dtype, hipStream_t st) {
   const C3Plan p = c3_plan(b, c, n, h, w, s);

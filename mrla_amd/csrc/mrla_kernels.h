@@ -230,6 +230,7 @@ int launch_conv1x1_wgrad_reduce_f32(const float* part, float* dw, int splits, in
 int conv3x3_wgrad_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
 int conv3x3_wgrad_preferred(int b, int c, int n, int h, int w, int s);
+int conv3x3_dgrad_flip_preferred(int b, int c, int n, int h, int w);
 int launch_conv3x3_wgrad(const void* dy, const void* x, float* part, void* dw, int dw_f32, int b, int c, int n, int h, int w,
                          int s, int dtype, hipStream_t st);
 // conv3x3_fwd.hip -- the forward of that convolution as an implicit GEMM (bf16 or fp16), y [b,ho,wo,n] from x [b,h,w,c] and
@@ -265,6 +266,8 @@ int launch_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float
                              hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
+// ... and the 3x3 weights of the flipped input-gradient route -> [n,3,3,c] copies and flipped transposes [c,3,3,n] in one launch
+int launch_conv3x3_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // light_nhwc_wide.hip -- the C % 64 == 0 forms on the LDS-DMA row pipeline (nhwc_rows.h)
 int launch_light_stats_fwd_wide(const void* x, const void* o, const float* wv, float* mom, void* xout, const float* psc,
                                 const float* psh, void* vout, int B, int C, int H, int W, int dtype, int act,

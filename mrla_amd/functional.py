@@ -166,6 +166,21 @@ CONV3X3_DGRAD = False   # the input gradient of an eligible stride-2 3x3 convolu
 conv3x3_dgrad = _switch("CONV3X3_DGRAD", "conv3x3_dgrad")
 
 
+CONV3X3_DGRAD_FLIP = True   # the input gradient of an eligible stride-1 3x3 convolution inside a model's forward (a Conv3x3Bank in
+#                             the bookkeeping scope), at a shape mrla_conv3x3_dgrad_flip_preferred answers 1 for (the large-batch
+#                             steps: profiles/conv3x3_dgrad_flip.md), is the stock FORWARD convolution of dy with the flipped,
+#                             transposed weight instead of the stock backward-data solver and the zero-fill of dX in front of
+#                             it.  The bank keeps that weight and the forward's 16-bit copy for all routed convolutions with
+#                             one launch per forward (mrla_conv3x3_weight_bank_refresh): no autocast cast kernel per
+#                             convolution either.  Forward values and the weight gradient are bit for bit what they were; dX
+#                             is the same sums from another solver.  False -- and every shape the rule answers 0 for, and every
+#                             call outside a model -- the very same autograd graph and launches as before;
+#                             conv3x3_dgrad_flip(False) turns it off for a block of code.
+
+
+conv3x3_dgrad_flip = _switch("CONV3X3_DGRAD_FLIP", "conv3x3_dgrad_flip")
+
+
 STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolution of three channels (stem_conv_applies: conv1 of
 #                      ResNet_mrlal) comes from mrla_stem_conv_wgrad -- fixed split, fixed summation order, no atomics --
 #                      written straight as the fp32 master weight's gradient.  The forward stays the stock operator's; the
@@ -238,9 +253,11 @@ def _ptr(t):
 # mask kernels per resnet50_mrlal step become one _foreach_add_ and one mask table.
 # ------------------------------------------------------------------------------------------------------
 class _Bookkeeping:
-    def __init__(self, n_drop_paths, bank=None):
+    def __init__(self, n_drop_paths, bank=None, bank3=None):
         self.counters, self.n_dp, self.table, self.key, self.next = [], int(n_drop_paths), None, None, 0
         self.bank = bank           # WeightBank of the model this forward belongs to (or None)
+        self.bank3 = bank3         # its Conv3x3Bank (or None), refreshed by the first routed convolution of this forward
+        self.bank3_fresh = False
 
     def drop_path_row(self, batch, drop_prob, device):
         """floor(keep + U[0,1)) / keep for one block: a row of a table drawn once per forward."""
@@ -262,11 +279,12 @@ def current_bookkeeping():
 
 
 @contextlib.contextmanager
-def batched_bookkeeping(n_drop_paths=0, bank=None):
+def batched_bookkeeping(n_drop_paths=0, bank=None, bank3=None):
     """Inside: train-mode BatchNorm counters handled by bn_act / the fused tails are collected and bumped with ONE
-    torch._foreach_add_ on exit, layers.drop_path_scale serves stochastic-depth rows from one table, and conv_bn_act
-    takes the 16-bit working copies of its weights from `bank` (a refreshed WeightBank)."""
-    prev, book = current_bookkeeping(), _Bookkeeping(n_drop_paths, bank)
+    torch._foreach_add_ on exit, layers.drop_path_scale serves stochastic-depth rows from one table, conv_bn_act
+    takes the 16-bit working copies of its weights from `bank` (a refreshed WeightBank), and conv3x3 those of the routed
+    3x3 convolutions from `bank3` (a Conv3x3Bank, which it refreshes once in here)."""
+    prev, book = current_bookkeeping(), _Bookkeeping(n_drop_paths, bank, bank3)
     _TLS.book = book
     try:
         yield book
@@ -1691,6 +1709,101 @@ class WeightBank:
         return self.entries.get(id(conv)) if dtype == self.dtype else None
 
 
+class Conv3x3Bank:
+    """16-bit working copies of a model's fp32 3x3-convolution weights whose stride-1 input gradient runs as a forward
+    convolution (CONV3X3_DGRAD_FLIP): per weight [n, c, 3, 3] the channels_last copy `w16` the forward multiplies with and
+    `wflip`, a channels_last [c, n, 3, 3] with wflip[c, n, kh, kw] = w16[n, c, 2 - kh, 2 - kw], the operand of
+    dX = conv(dY, wflip) -- all of them written by ONE launch of mrla_conv3x3_weight_bank_refresh per forward: what
+    torch.autocast does with one cast kernel per convolution and forward, and what the permutation costs two elementwise
+    kernels per input gradient for.
+    Built lazily: a convolution becomes a member when conv3x3 first routes it (get()), so a model none of whose shapes is
+    routed never calls the entry point.  A first build, a new member, moved parameters or another dtype rebuild the table
+    with a host-to-device copy: not capturable -- run one forward eagerly before capturing, as for the WeightBank.
+    get() refreshes at most once per bookkeeping scope (once per forward), under WeightBank.refresh's conditions: whenever
+    gradients are enabled, whenever a HIP graph is being captured, and ALWAYS once a refresh has been captured (replays
+    move the masters without touching a version counter); `invalidate()` after writes the counters cannot see."""
+
+    def __init__(self):
+        self.members, self.entries = [], {}          # convolutions in the order they were first routed; id -> (w16, wflip)
+        self.sig = self.key = self.table = None
+        self.dtype = torch.bfloat16
+        self.captured = False          # sticky: a refresh is part of some HIP graph
+        self.max_tiles = 1
+        self._tables = []              # tables a captured refresh may still read
+
+    def invalidate(self):
+        """Force the next refresh to re-cast (after weight updates that bypass the version counters)."""
+        self.key = None
+
+    @staticmethod
+    def eligible(conv):
+        if not (type(conv) is torch.nn.Conv2d and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+                and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == "zeros"
+                and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0):
+            return False
+        w = conv.weight
+        return (w.is_cuda and w.dtype == torch.float32 and w.data_ptr() % 16 == 0
+                and (w.is_contiguous() or w.is_contiguous(memory_format=_CL)))
+
+    def _signature(self, dtype):
+        return (dtype,) + tuple((id(c), c.weight.data_ptr(), c.weight.is_contiguous()) for c in self.members)
+
+    def _build(self, dtype, what):
+        if torch.cuda.is_current_stream_capturing():      # (the table is built with a host-to-device copy: not capturable)
+            raise L.MrlaHipError(f"Conv3x3Bank: {what} inside a HIP graph capture; run one forward of the model eagerly before "
+                                 "capturing it (in the precision of the capture)")
+        self.members = [c for c in self.members if self.eligible(c)]
+        if dtype != self.dtype:
+            self.entries = {}
+        self.dtype, rows, entries, self.max_tiles = dtype, [], {}, 1
+        for c in self.members:
+            w, n, k = c.weight, c.out_channels, c.in_channels
+            held = self.entries.get(id(c))
+            if held is None or held[0].device != w.device:
+                held = (torch.empty((n, k, 3, 3), dtype=dtype, device=w.device, memory_format=_CL),
+                        torch.empty((k, n, 3, 3), dtype=dtype, device=w.device, memory_format=_CL))
+            entries[id(c)] = held
+            rows.append([w.data_ptr(), held[0].data_ptr(), held[1].data_ptr(), (n << 32) | k, 0 if w.is_contiguous() else 1])
+            self.max_tiles = max(self.max_tiles, 9 * (n // 64) * (k // 64))
+        self.entries = entries
+        if self.captured and self.table is not None:
+            self._tables.append(self.table)
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.members[0].weight.device) if rows else None
+        self.sig, self.key = self._signature(dtype), None
+
+    def _refresh(self, dtype):
+        if self._signature(dtype) != self.sig or not all(self.eligible(c) for c in self.members):
+            self._build(dtype, "moved parameters or a change of dtype")
+        if self.table is None:
+            return
+        key = tuple(c.weight._version for c in self.members)
+        self.captured = self.captured or torch.cuda.is_current_stream_capturing()
+        if key != self.key or self.captured or torch.is_grad_enabled():
+            with torch.cuda.device(self.table.device):
+                L.call("mrla_conv3x3_weight_bank_refresh", _ptr(self.table), len(self.members), self.max_tiles,
+                       _DT[self.dtype], _stream())
+            self.key = key
+
+    def get(self, conv, dtype, book):
+        """(w16, wflip) of `conv` in `dtype` (torch.bfloat16 or torch.float16), as of this forward -- `book`: its bookkeeping
+        scope, which remembers that the refresh ran -- or None for a convolution the bank does not take."""
+        if dtype not in (torch.bfloat16, torch.float16) or not self.eligible(conv):
+            return None
+        if id(conv) not in self.entries or dtype != self.dtype:
+            if not any(c is conv for c in self.members):
+                self.members.append(conv)
+            try:
+                self._build(dtype, "first use of a convolution (or a change of dtype)")
+            except L.MrlaHipError:
+                self.members = [c for c in self.members if id(c) in self.entries]
+                raise
+            book.bank3_fresh = False
+        if not book.bank3_fresh:
+            self._refresh(dtype)
+            book.bank3_fresh = True
+        return self.entries.get(id(conv))
+
+
 class _GemmState:
     """What the backward of the 1x1 GEMM convolution needs beside its saved tensors (x, w, w16t); holds no tensor."""
     __slots__ = ("sub", "wshape", "wstride", "wdtype", "f32")
@@ -2115,11 +2228,14 @@ def _own_wgrad(ctx, entry, rows_entry, dy, x, shape, taps):
     return gw
 
 
-def _working_weight(ctx, x, w, for_kernel):
+def _working_weight(ctx, x, w, for_kernel, banked=None):
     """The weight a spatial convolution node computes on: `w` cast to x's dtype as autocast casts it -- and, where one of the
-    own kernels reads it (`for_kernel`: as [n, kh, kw, c], 16 bytes a lane), channels_last and 16-byte aligned.  The
+    own kernels reads it (`for_kernel`: as [n, kh, kw, c], 16 bytes a lane), channels_last and 16-byte aligned; with
+    `banked` (Conv3x3Bank.get: (w16, wflip)) that is the bank's copy, the same bits with no kernel launched here.  The
     weight's own shape, strides and dtype are noted on `ctx` for the gradient."""
     ctx.wshape, ctx.wstride, ctx.wdtype = w.shape, w.stride(), w.dtype
+    if banked is not None:
+        return banked[0]
     w16 = w if w.dtype == x.dtype else w.to(x.dtype)
     if for_kernel:
         w16 = w16.contiguous(memory_format=_CL)
@@ -2142,10 +2258,12 @@ _OWN_WGRAD_F32 = {3: ("mrla_conv3x3_f32_wgrad", "mrla_conv3x3_f32_wgrad_rows")} 
 def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=False):
     """(gx, gw) of a spatial convolution node that saved (x, working weight) and noted ctx.stride: the weight gradient from
     the own kernel if `own_wgrad` (the entry point by x's dtype); the input gradient from the own forward on the flipped,
-    transposed weight (a pure permutation) if `flipped_dgrad` at stride 1, from mrla_conv3x3_dgrad_s2 if `own_dgrad` -- each only for a gradient of x's
+    transposed weight (a pure permutation) if `flipped_dgrad` at stride 1 -- where the node saved the bank's flipped weight
+    behind the two (CONV3X3_DGRAD_FLIP) that one, and without `flipped_dgrad` the stock forward convolution on it --, from
+    mrla_conv3x3_dgrad_s2 if `own_dgrad` -- each only for a gradient of x's
     dtype at a 16-byte-aligned address; whatever is asked for and still missing from the stock backward, masked to exactly
     that; the weight gradient in the weight's own dtype and strides (autograd's / DDP's layout contract)."""
-    x, w16 = ctx.saved_tensors
+    x, w16, *banked_flip = ctx.saved_tensors
     dy = dy.contiguous(memory_format=_CL)
     b, c, h, wd = x.shape
     n, k = w16.shape[0], w16.shape[2]
@@ -2156,11 +2274,15 @@ def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=Fa
     if need_w and own and own_wgrad and k in entries:
         shape = (b, c, n, h, wd, ctx.stride[0]) if k == 3 else (b, n, h, wd)
         gw = _own_wgrad(ctx, *entries[k], dy, x, shape, (k, k, c))
-    if need_x and own and flipped_dgrad and ctx.stride[0] == 1:
-        wflip = w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)       # [c, 3, 3, n] in memory
-        gx = torch.empty_like(x)
-        _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
-              b, n, c, h, wd, 1, _DT[x.dtype], _stream())
+    if need_x and own and ctx.stride[0] == 1 and (flipped_dgrad or banked_flip):
+        # [c, 3, 3, n] in memory: the bank's, or two elementwise kernels
+        wflip = banked_flip[0] if banked_flip else w16.flip(2, 3).transpose(0, 1).contiguous(memory_format=_CL)
+        if flipped_dgrad:
+            gx = torch.empty_like(x)
+            _call("mrla_conv3x3_fwd", (dy.numel() + gx.numel()) * x.element_size(), _ptr(dy), _ptr(wflip), _ptr(gx), None,
+                  b, n, c, h, wd, 1, _DT[x.dtype], _stream())
+        else:              # every element of dX is written: no zero-fill, and the forward solver of the layer's own shape
+            gx = torch.ops.aten.convolution(dy, wflip, None, (1, 1), (1, 1), (1, 1), False, (0, 0), 1)
     if need_x and own and own_dgrad:
         gx = _own_dgrad_s2(dy, x, w16)
     need_x, need_w = need_x and gx is None, need_w and gw is None
@@ -2236,16 +2358,16 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, stride, own_wgrad, own_dgrad):
+    def forward(ctx, x, w, stride, own_wgrad, own_dgrad, banked):
         ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
-        w16 = _working_weight(ctx, x, w, own_dgrad)
-        ctx.save_for_backward(x, w16)
+        w16 = _working_weight(ctx, x, w, own_dgrad, banked)
+        ctx.save_for_backward(x, w16, *(() if banked is None else banked[1:]))
         return torch.ops.aten.convolution(x, w16, None, ctx.stride, (1, 1), (1, 1), False, (0, 0), 1)
 
     @staticmethod
     @_on_device
     def backward(ctx, dy):
-        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, own_dgrad=ctx.own_dgrad) + (None,) * 3
+        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, own_dgrad=ctx.own_dgrad) + (None,) * 4
 
 
 def conv3x3_fwd_applies(conv, x):
@@ -2282,10 +2404,10 @@ class _Conv3x3FwdFn(torch.autograd.Function):
 
     @staticmethod
     @_on_device
-    def forward(ctx, x, w, stride, moments, own_wgrad, own_dgrad):
+    def forward(ctx, x, w, stride, moments, own_wgrad, own_dgrad, banked):
         ctx.set_materialize_grads(False)
         ctx.stride, ctx.own_wgrad, ctx.own_dgrad = (stride, stride), own_wgrad, own_dgrad
-        w16 = _working_weight(ctx, x, w, True)
+        w16 = _working_weight(ctx, x, w, True, banked)
         b, c, h, wd = x.shape
         n, dt = w16.shape[0], _DT[x.dtype]
         ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
@@ -2297,7 +2419,7 @@ class _Conv3x3FwdFn(torch.autograd.Function):
             part = torch.empty((0,), dtype=torch.float32, device=x.device)
         _call("mrla_conv3x3_fwd", (x.numel() + y.numel()) * x.element_size(), _ptr(x), _ptr(w16), _ptr(y),
               _ptr(part) if moments else None, b, c, n, h, wd, stride, dt, _stream())
-        ctx.save_for_backward(x, w16)
+        ctx.save_for_backward(x, w16, *(() if banked is None else banked[1:]))
         ctx.mark_non_differentiable(part)
         return y, part
 
@@ -2305,14 +2427,40 @@ class _Conv3x3FwdFn(torch.autograd.Function):
     @_on_device
     def backward(ctx, dy, _dpart=None):
         if dy is None:
-            return None, None, None, None, None, None
-        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, flipped_dgrad=True, own_dgrad=ctx.own_dgrad) + (None,) * 4
+            return (None,) * 7
+        return _spatial_conv_backward(ctx, dy, own_wgrad=ctx.own_wgrad, flipped_dgrad=True, own_dgrad=ctx.own_dgrad) + (None,) * 5
+
+
+_DGRAD_FLIP_PREFERRED = {}      # (b, c, n, h, w, dtype code) -> mrla_conv3x3_dgrad_flip_preferred(...) == 1
+
+
+def _conv3x3_banked(conv, x, by_rule):
+    """(w16, wflip) of `conv` from the Conv3x3Bank of the running forward, refreshed for it -- or None: CONV3X3_DGRAD_FLIP
+    off, no bank (a call outside a model's bookkeeping), not a stride-1 convolution the own spatial kernels' module, layout
+    and dtype conditions hold for, grad mode off or an input that wants no gradient, a weight the bank does not take, and,
+    `by_rule`, a shape mrla_conv3x3_dgrad_flip_preferred answers 0 for (asked once per shape)."""
+    book = current_bookkeeping()
+    if not CONV3X3_DGRAD_FLIP or book is None or book.bank3 is None:
+        return None
+    dt = _spatial_conv_applies(conv, x, (3, 3), ((1, 1),), (1, 1), False)
+    if dt is None or not (torch.is_grad_enabled() and x.requires_grad):
+        return None
+    if by_rule:
+        b, c, h, w = x.shape
+        key = (b, c, conv.out_channels, h, w, _DT[dt])
+        hit = _DGRAD_FLIP_PREFERRED.get(key)
+        if hit is None:
+            hit = _DGRAD_FLIP_PREFERRED[key] = L.load().mrla_conv3x3_dgrad_flip_preferred(*key) == 1
+        if not hit:
+            return None
+    return book.bank3.get(conv, dt, book)
 
 
 def _conv3x3_own(x, conv, moments):
     dt = _conv_compute_dtype(x)
     return _Conv3x3FwdFn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], moments,
-                               _conv3x3_own_wgrad(conv, x), CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x))
+                               _conv3x3_own_wgrad(conv, x), CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x),
+                               _conv3x3_banked(conv, x, False))
 
 
 def conv3x3(x, conv):
@@ -2320,17 +2468,19 @@ def conv3x3(x, conv):
     block).  With CONV3X3_FWD on and conv3x3_fwd_applies: one autograd node on mrla_conv3x3_fwd (_Conv3x3FwdFn).  Else, where
     neither the own weight gradient (conv3x3_applies, and CONV3X3_WGRAD or CONV3X3_WGRAD_AUTO at a shape
     mrla_conv3x3_wgrad_preferred answers 1 for; in fp32 conv3x3_f32_applies and CONV3X3_WGRAD_F32) nor CONV3X3_DGRAD with
-    conv3x3_dgrad_applies holds, it IS conv(x): the same autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn)
+    conv3x3_dgrad_applies holds, nor the stride-1 input gradient is routed to the stock forward on the banked flipped weight
+    (CONV3X3_DGRAD_FLIP: _conv3x3_banked), it IS conv(x): the same autograd graph as before.  Otherwise one autograd node (_Conv3x3Fn)
     whose forward is the stock operator's, whose weight gradient is mrla_conv3x3_wgrad's (fp32: mrla_conv3x3_f32_wgrad's)
     under the first and whose input gradient is mrla_conv3x3_dgrad_s2's under the second."""
     if CONV3X3_FWD and conv3x3_fwd_applies(conv, x):
         return _conv3x3_own(x, conv, False)[0]
     own_wgrad = _conv3x3_own_wgrad(conv, x) or (CONV3X3_WGRAD_F32 and conv3x3_f32_applies(conv, x))
     own_dgrad = CONV3X3_DGRAD and conv3x3_dgrad_applies(conv, x)
-    if not (own_wgrad or own_dgrad):
+    banked = _conv3x3_banked(conv, x, True)
+    if not (own_wgrad or own_dgrad or banked):
         return conv(x)
     dt = _conv_compute_dtype(x)
-    return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], own_wgrad, own_dgrad)
+    return _Conv3x3Fn.apply(x if x.dtype == dt else x.to(dt), conv.weight, conv.stride[0], own_wgrad, own_dgrad, banked)
 
 
 def conv3x3_bn_act(x, conv, bn, relu, defer=False):

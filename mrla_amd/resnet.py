@@ -269,6 +269,13 @@ class _ResNetMRLA(nn.Module):
             return None                            # fp32 runs multiply with the master weights themselves
         return bank.refresh()
 
+    def _conv3x3_bank(self):
+        """This network's Conv3x3Bank: empty until F_.conv3x3 routes a convolution to it (CONV3X3_DGRAD_FLIP)."""
+        bank = self.__dict__.get("_bank3")
+        if bank is None:
+            bank = self.__dict__["_bank3"] = F_.Conv3x3Bank()
+        return bank
+
     def _stochastic_depth_blocks(self):
         """Blocks that will draw a stochastic-depth mask in this forward (0: none, each block draws its own)."""
         if not (self.training and self.drop_path):
@@ -318,7 +325,8 @@ class ResNet_mrlal(_ResNetMRLA):
     def forward_features(self, x):
         if self.channels_last and x.is_cuda:
             x = _to_channels_last(x)
-        with F_.batched_bookkeeping(self._stochastic_depth_blocks(), self._weight_bank() if x.is_cuda else None):
+        with F_.batched_bookkeeping(self._stochastic_depth_blocks(), self._weight_bank() if x.is_cuda else None,
+                                    self._conv3x3_bank() if x.is_cuda else None):
             x = F_.bn_relu_maxpool(F_.stem_conv(x, self.conv1), self.bn1, self.maxpool)
             return self.layer4(self.layer3(self.layer2(self.layer1(x))))
 
@@ -369,7 +377,8 @@ class ResNet_mrlab(_ResNetMRLA):
     def forward_features(self, x):
         if self.channels_last and x.is_cuda:
             x = _to_channels_last(x)
-        with F_.batched_bookkeeping(self._stochastic_depth_blocks(), self._weight_bank() if x.is_cuda else None):
+        with F_.batched_bookkeeping(self._stochastic_depth_blocks(), self._weight_bank() if x.is_cuda else None,
+                                    self._conv3x3_bank() if x.is_cuda else None):
             x = F_.bn_relu_maxpool(self.conv1(x), self.bn1, self.maxpool)
             k = v = None
             for stage in self.stages:
