@@ -796,6 +796,30 @@ int mrla_conv3x3_f32_wgrad_plan(int b, int c, int n, int h, int w, int stride, i
 int mrla_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int c, int n, int h, int w,
                            int stride, void* stream);
 
+/* The weight gradient of the stem convolution (7x7, stride 2, padding 3, dilation 1, groups 1, three input channels) for the
+ * same fp32 recipe: three ADDITIVE symbols, MRLA_ABI_VERSION stays 5, and mrla_stem_conv_wgrad* above go on refusing MRLA_F32.
+ *     dw[n, kh, kw, c] = sum_{b, y, x} dy[b, y, x, n] * x[b, 2y + kh - 3, 2x + kw - 3, c]        kh, kw in 0..6, c in 0..2
+ *   x: [b, h, w, 3] and dy: [b, ho, wo, n] channels_last fp32 activations, ho = (h-1)/2 + 1, wo = (w-1)/2 + 1; taps outside an
+ *   image contribute nothing (the row above an image is not the previous image's last); dw: [n, 7, 7, 3] fp32 -- a
+ *   [n, 3, 7, 7] tensor in channels_last memory format;
+ *   part: fp32 workspace [rows, n, 7, 7, 3] with rows = mrla_stem_conv_f32_wgrad_rows(...): the per-workgroup partial tiles of
+ *   the fixed split over output rows, summed in ascending order by a second kernel.
+ * Every product is a fused multiply-add on the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32), each partial sum one chain in
+ * a fixed order.  No atomics and no memset: every element of part and dw is written exactly once per call, nothing is read
+ * outside x and dy, and the result is a function of the arguments alone -- bit-identical from call to call, eagerly and from
+ * a replayed graph.
+ * MRLA_EUNSUPPORTED unless n % 64 == 0, b * h * w * 3 * 4 < 2^31 (the bytes of x) and b * ho * wo * n * 4 < 2^31 (the bytes of
+ * dy; batch 256 at 224 x 224 is served); any b, h, w >= 1 within that: odd heights, odd widths, maps smaller than the kernel,
+ * rows wider than one step (cut into column segments).  MRLA_EINVAL, decided on the host before anything is launched: a
+ * non-positive dimension, a NULL pointer (`out` included), a pointer that is not 16-byte aligned.  The queries answer the
+ * same code as the launch for the same arguments.
+ * mrla_stem_conv_f32_wgrad_plan: `out` is a HOST array of 7 ints, the meaning of mrla_stem_conv_wgrad_plan's: tile n, output
+ * rows per split, splits (= mrla_stem_conv_f32_wgrad_rows()), column segments per row, LDS bytes of a workgroup (<= 81920),
+ * output columns per segment, output rows per step.  Split i takes the rows [i * out[1], min(b * ho, (i + 1) * out[1])). */
+int mrla_stem_conv_f32_wgrad_rows(int b, int n, int h, int w);      /* rows of part (> 0), or a negative code */
+int mrla_stem_conv_f32_wgrad_plan(int b, int n, int h, int w, int* out);
+int mrla_stem_conv_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int n, int h, int w, void* stream);
+
 /* The 16-bit working copies of every fp32 convolution weight the GEMMs above multiply with, refreshed in ONE launch per
  * training step instead of one autocast cast kernel per convolution and forward (and one transposing copy per input
  * gradient): replaces what torch.autocast does in front of nn.Conv2d (resnet/train.py runs fp32; the bf16 configuration of

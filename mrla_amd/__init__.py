@@ -34,7 +34,10 @@ def __getattr__(name):
     if name == "stem_wgrad":      # the switch of the own stem (7x7 / stride 2) weight gradient (functional.STEM_WGRAD)
         from . import functional
         return functional.stem_wgrad
-    if name == "reproducible_gradients":      # all of them (the fp32 3x3 one included): every parameter gradient a function of the step's inputs alone
+    if name == "stem_wgrad_f32":      # ... and of the fp32 stem weight gradient outside autocast (functional.STEM_WGRAD_F32)
+        from . import functional
+        return functional.stem_wgrad_f32
+    if name == "reproducible_gradients":      # all of them (the fp32 3x3 and stem ones included): every parameter gradient a function of the step's inputs alone
         from . import functional
         return functional.reproducible_gradients
     raise AttributeError(f"module 'mrla_amd' has no attribute {name!r}")

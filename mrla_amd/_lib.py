@@ -129,6 +129,9 @@ SIGNATURES = {
     "mrla_stem_conv_wgrad_rows": [_I] * 5,
     "mrla_stem_conv_wgrad_plan": [_I] * 5 + [_P],
     "mrla_stem_conv_wgrad": [_P, _P, _P, _P] + [_I] * 6 + [_P],
+    "mrla_stem_conv_f32_wgrad_rows": [_I] * 4,
+    "mrla_stem_conv_f32_wgrad_plan": [_I] * 4 + [_P],
+    "mrla_stem_conv_f32_wgrad": [_P, _P, _P, _P] + [_I] * 4 + [_P],
     "mrla_weight_bank_refresh": [_P, _I, _I, _P],
     "mrla_weight_bank_refresh_dt": [_P, _I, _I, _I, _P],
     "mrla_conv3x3_weight_bank_refresh": [_P, _I, _I, _I, _P],
@@ -236,6 +239,12 @@ def stem_conv_wgrad_plan(b, n, h, w, dtype=None):
     """(tile n, output rows per split, splits, column segments per row, LDS bytes, output columns per segment, output rows
     per step) of mrla_stem_conv_wgrad, or None."""
     return _plan("mrla_stem_conv_wgrad_plan", 7, b, n, h, w, dtype)
+
+
+def stem_conv_f32_wgrad_plan(b, n, h, w):
+    """(tile n, output rows per split, splits, column segments per row, LDS bytes, output columns per segment, output rows
+    per step) of mrla_stem_conv_f32_wgrad, or None."""
+    return _plan("mrla_stem_conv_f32_wgrad_plan", 7, b, n, h, w)
 
 
 def bn_pool_plan(b, c, h, w, dtype, band=0):

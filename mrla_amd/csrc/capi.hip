@@ -934,6 +934,30 @@ int mrla_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* 
   return launch_conv3x3_f32_wgrad(dy, x, part, dw, b, c, n, h, w, stride, (hipStream_t)stream);
 }
 
+// The fp32 stem weight gradient (stem_wgrad_f32.hip): symbols of its own -- mrla_stem_conv_wgrad* go on refusing MRLA_F32.  One
+// argument check for the queries and the launch, so that they answer the same code for the same arguments.
+static int stem_conv_f32_args(int b, int n, int h, int w) { return (b <= 0 || n <= 0 || h <= 0 || w <= 0) ? MRLA_EINVAL : MRLA_OK; }
+
+int mrla_stem_conv_f32_wgrad_rows(int b, int n, int h, int w) {
+  const int rc = stem_conv_f32_args(b, n, h, w);
+  return rc != MRLA_OK ? rc : stem_conv_f32_wgrad_rows(b, n, h, w);
+}
+
+int mrla_stem_conv_f32_wgrad_plan(int b, int n, int h, int w, int* out) {
+  if (!out) return MRLA_EINVAL;
+  const int rc = stem_conv_f32_args(b, n, h, w);
+  return rc != MRLA_OK ? rc : stem_conv_f32_wgrad_plan(b, n, h, w, out);
+}
+
+int mrla_stem_conv_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int n, int h, int w, void* stream) {
+  if (!dy || !x || !part || !dw) return MRLA_EINVAL;
+  // a lane moves 16 bytes of dy and part, and four elements of dw (x: aligned dwords; the same rule for all four)
+  if (((uintptr_t)dy | (uintptr_t)x | (uintptr_t)part | (uintptr_t)dw) & 15) return MRLA_EINVAL;
+  const int rc = stem_conv_f32_args(b, n, h, w);
+  if (rc != MRLA_OK) return rc;
+  return launch_stem_conv_f32_wgrad(dy, x, part, dw, b, n, h, w, (hipStream_t)stream);
+}
+
 int mrla_conv1x1_wgrad_bn_supported(int m, int k, int n, int dtype) {
   const int rc = conv1x1_args(m, k, n, dtype);
   return rc != MRLA_OK ? rc : conv1x1_wgrad_bn_supported(m, k, n);

@@ -264,6 +264,12 @@ int conv3x3_f32_wgrad_rows(int b, int c, int n, int h, int w, int s);
 int conv3x3_f32_wgrad_plan(int b, int c, int n, int h, int w, int s, int* out);
 int launch_conv3x3_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int c, int n, int h, int w, int s,
                              hipStream_t st);
+// stem_wgrad_f32.hip -- the weight gradient of the stem's 7x7 / stride 2 / padding 3 convolution of three channels of fp32
+// operands on that MFMA, dW [n,7,7,3] fp32; part [rows][n][7][7][3]
+int stem_conv_f32_wgrad_rows(int b, int n, int h, int w);
+int stem_conv_f32_wgrad_plan(int b, int n, int h, int w, int* out);
+int launch_stem_conv_f32_wgrad(const float* dy, const float* x, float* part, float* dw, int b, int n, int h, int w,
+                               hipStream_t st);
 // weight_bank.hip -- all eligible fp32 conv weights -> bf16 or fp16 copies (+ transposes) in one launch
 int launch_weight_bank_refresh(const long long* table, int entries, int max_tiles, int dtype, hipStream_t st);
 // ... and the 3x3 weights of the flipped input-gradient route -> [n,3,3,c] copies and flipped transposes [c,3,3,n] in one launch

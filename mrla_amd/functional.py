@@ -192,13 +192,26 @@ STEM_WGRAD = False   # the weight gradient of the stem's 7x7 / stride 2 convolut
 stem_wgrad = _switch("STEM_WGRAD", "stem_wgrad")
 
 
+STEM_WGRAD_F32 = False   # the weight gradient of the same convolution of an fp32 input outside autocast (stem_conv_f32_applies:
+#                          the recipe of resnet/train.py:397-409) comes from mrla_stem_conv_f32_wgrad -- the fixed split and
+#                          summation order of mrla_stem_conv_wgrad on the exact fp32-input MFMA, no atomics: a function of its
+#                          arguments, eagerly and from a replayed graph.  The forward stays the stock operator's.  False (the
+#                          default): conv(x) itself, the very same autograd graph and launches as before; stem_wgrad_f32()
+#                          turns it on for a block of code, reproducible_gradients() together with the other three switches.
+#                          STEM_WGRAD never routes fp32, STEM_WGRAD_F32 never routes 16-bit.  profiles/stem_wgrad_f32.md has
+#                          the numbers a default would rest on.
+
+
+stem_wgrad_f32 = _switch("STEM_WGRAD_F32", "stem_wgrad_f32")
+
+
 @contextlib.contextmanager
 def reproducible_gradients(enabled=True):
-    """CONV3X3_WGRAD, CONV3X3_WGRAD_F32 and STEM_WGRAD = `enabled` inside the block: with them on no weight gradient of a
-    bf16 or fp16 resnet*_mrlal step is left to an atomic split-K solver, and in an fp32 step (no autocast) none of a 3x3
-    convolution.  In fp32 the stem's 7x7 gradient is still the stock operator's: there is no fp32 stem kernel.  The previous
-    values come back on exit, also when the block raises."""
-    with conv3x3_wgrad(enabled), conv3x3_wgrad_f32(enabled), stem_wgrad(enabled):
+    """CONV3X3_WGRAD, CONV3X3_WGRAD_F32, STEM_WGRAD and STEM_WGRAD_F32 = `enabled` inside the block: with them on no weight
+    gradient of a bf16 or fp16 resnet*_mrlal step is left to an atomic split-K solver, and none of an fp32 step (no autocast)
+    either: the 3x3 gradients come from mrla_conv3x3_f32_wgrad and the stem's 7x7 gradient from mrla_stem_conv_f32_wgrad (the
+    1x1 GEMMs' under fp32_gemms()).  The previous values come back on exit, also when the block raises."""
+    with conv3x3_wgrad(enabled), conv3x3_wgrad_f32(enabled), stem_wgrad(enabled), stem_wgrad_f32(enabled):
         yield
 
 
@@ -2252,7 +2265,8 @@ def _weight_strides(ctx, gw):
 
 
 _OWN_WGRAD = {3: ("mrla_conv3x3_wgrad", "mrla_conv3x3_wgrad_rows"), 7: ("mrla_stem_conv_wgrad", "mrla_stem_conv_wgrad_rows")}
-_OWN_WGRAD_F32 = {3: ("mrla_conv3x3_f32_wgrad", "mrla_conv3x3_f32_wgrad_rows")}      # an fp32 x and an fp32 weight
+_OWN_WGRAD_F32 = {3: ("mrla_conv3x3_f32_wgrad", "mrla_conv3x3_f32_wgrad_rows"),      # an fp32 x and an fp32 weight
+                  7: ("mrla_stem_conv_f32_wgrad", "mrla_stem_conv_f32_wgrad_rows")}
 
 
 def _spatial_conv_backward(ctx, dy, own_wgrad, flipped_dgrad=False, own_dgrad=False):
@@ -2506,12 +2520,26 @@ def stem_conv_applies(conv, x):
     return L.load().mrla_stem_conv_wgrad_rows(b, conv.out_channels, h, w, _DT[dt]) > 0
 
 
+def stem_conv_f32_applies(conv, x):
+    """True when the weight gradient of `conv(x)` belongs on mrla_stem_conv_f32_wgrad: the module conditions of
+    stem_conv_applies (a bias-free nn.Conv2d 7x7 / stride (2, 2) / padding (3, 3) / dilation 1 / groups 1 of three input
+    channels, zero padding), grad mode and an fp32 CUDA weight that wants its gradient, a CUDA channels_last 16-byte-aligned
+    fp32 input that the convolution computes in fp32 (no autocast), and a shape the kernel takes
+    (mrla_stem_conv_f32_wgrad_rows).  stem_conv_applies goes on answering False for all of these."""
+    dt = _spatial_conv_applies(conv, x, (7, 7), ((2, 2),), (3, 3), True, dtypes=(torch.float32,))
+    if dt is None or conv.in_channels != 3 or x.dtype != torch.float32 or conv.weight.dtype != torch.float32:
+        return False
+    b, _, h, w = x.shape
+    return L.load().mrla_stem_conv_f32_wgrad_rows(b, conv.out_channels, h, w) > 0
+
+
 class _StemConvFn(torch.autograd.Function):
     """y = conv2d(x, w, stride 2, padding 3) of a channels_last bf16 or fp16 three-channel `x` by the stock operator, on `w`
     cast to x's dtype as autocast casts it.  Backward: dW [n, 7, 7, 3] from mrla_stem_conv_wgrad in the weight's own dtype --
     for an fp32 master weight the fp32 sums themselves -- returned as [n, 3, 7, 7] with the weight's strides.  The stock
     backward runs only for what is left: dX if `x` itself needs a gradient (the image batch does not), and dW where dy arrives
-    in another dtype or misaligned."""
+    in another dtype or misaligned.  An fp32 `x` with an fp32 `w` (STEM_WGRAD_F32 and stem_conv_f32_applies at the call) is
+    the same node: dW then comes from mrla_stem_conv_f32_wgrad."""
 
     @staticmethod
     @_on_device
@@ -2528,10 +2556,11 @@ class _StemConvFn(torch.autograd.Function):
 
 
 def stem_conv(x, conv):
-    """conv(x) for the stem's 7x7 / stride 2 convolution (resnet_mrla_light.py: conv1).  With STEM_WGRAD off, or where
-    stem_conv_applies says no, it IS conv(x): the same autograd graph as before.  Otherwise one autograd node whose forward is
-    the stock operator's and whose weight gradient is mrla_stem_conv_wgrad's."""
-    if not (STEM_WGRAD and stem_conv_applies(conv, x)):
+    """conv(x) for the stem's 7x7 / stride 2 convolution (resnet_mrla_light.py: conv1).  Where neither STEM_WGRAD with
+    stem_conv_applies nor STEM_WGRAD_F32 with stem_conv_f32_applies holds, it IS conv(x): the same autograd graph as before.
+    Otherwise one autograd node whose forward is the stock operator's and whose weight gradient is mrla_stem_conv_wgrad's
+    (fp32: mrla_stem_conv_f32_wgrad's)."""
+    if not ((STEM_WGRAD and stem_conv_applies(conv, x)) or (STEM_WGRAD_F32 and stem_conv_f32_applies(conv, x))):
         return conv(x)
     dt = _conv_compute_dtype(x)
     return _StemConvFn.apply(x if x.dtype == dt else x.to(dt), conv.weight)

@@ -1,7 +1,9 @@
 """Run-to-run difference of one FP32 training step's gradients (no autocast) with functional.CONV3X3_WGRAD_F32 off and on: the
 run-to-run table of profiles/conv3x3_wgrad_f32.md, by the protocol of scripts/conv3x3_grad_noise.py.
-    python scripts/conv3x3_f32_grad_noise.py [batch] [deterministic]
-The stock library runs in find mode (torch.backends.cudnn.benchmark) unless `deterministic` is given.  resnet50_mrlal, fp32,
+    python scripts/conv3x3_f32_grad_noise.py [batch] [deterministic] [reproducible]
+The stock library runs in find mode (torch.backends.cudnn.benchmark) unless `deterministic` is given.  With `reproducible` the
+whole run is inside mrla_amd.reproducible_gradients() (the fp32 stem gradient from mrla_stem_conv_f32_wgrad in both settings;
+`off` then switches only the 3x3 gradients back to the stock operator): profiles/stem_wgrad_f32.md.  resnet50_mrlal, fp32,
 224 x 224, the same weights and data: per setting one warm-up step, then the step is run twice and the two sets of gradients are
 compared -- relative L2 over all parameters and over the 3x3 convolution weights, and how many parameters' gradients are
 bit-equal.  The last line compares the 3x3 weight gradients of the last `on` step with those of the last `off` step."""
@@ -33,9 +35,12 @@ is3 = sorted(name + ".weight" for name, m in net.named_modules()
 losses, last = [], {}
 
 
+reproducible = "reproducible" in sys.argv[2:]
+
+
 def grads(on):
     net.zero_grad(set_to_none=True)
-    with mrla_amd.conv3x3_wgrad_f32(on):
+    with mrla_amd.reproducible_gradients(True) if reproducible else contextlib.nullcontext(), mrla_amd.conv3x3_wgrad_f32(on):
         loss = torch.nn.functional.cross_entropy(net(x), y)
         loss.backward()
     losses.append(float(loss))
